@@ -8,7 +8,11 @@ hypotheses (48,24,8), batch 1 per rank (BASELINE.json configs[1]); synthetic DTU
 
 A "step" = one reference-view inference (one CoreNet.forward, B=1) with the inputs already resident in HBM.
 Views shard across ranks with no data-path collective (eval items are independent): weak scaling.
-Rank 0 prints ONE JSON line; it also carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times EXACTLY --steps steps (one block), writes the last step's
+outputs if --dump-outputs DIR is given, and prints the headline (`metric`, `value`, `unit`, `ms_per_step`, ...).
+With --full it also repeats the timed block (median of >= 3 blocks, >= 1 s of timed work in all, unless --blocks says
+otherwise), and the line also carries
+  one_at_a_time the same steps with a single view in flight
   roofline      the dominant hand-written kernel family (by time), measured live with HIP events on the launch
                 stream in a separate profile pass: algorithmic flops (or bytes) / summed launch time vs CDNA4 peak
   kernels       the same for every hand-written kernel family + the stock (MIOpen) remainder
@@ -22,6 +26,9 @@ Rank 0 prints ONE JSON line; it also carries
   cfg4          BASELINE configs[3]: 1920x1056 with 7 and 11 views, views/s (rank 0, N=1)
   cfg5_scan     BASELINE configs[4], one scan: 49 items with the cross-item feature cache + the fused consistency filter (rank 0, N=1)
 The headline `value` / `config` are the eval figures for every N; the blocks above are extra keys of the same line.
+
+    python bench.py --gpus 1 --steps 200 --warmup 10 --dump-outputs bench_outputs     # + depth.npy, confidence.npy
+    python bench.py --gpus 1 --full                                                   # every block above
 """
 import argparse
 import math
@@ -776,6 +783,27 @@ def cpu_baseline(timed_views=3):
                       f"all {[round(t, 2) for t in times]}"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, directory):
+    """The arrays the timed path handed its caller in its last step (CoreNet.forward's dict: depth, confidence) ->
+    DIR/<name>.npy, float32 (float64 stays float64).  The inputs are seeded, so two builds can be compared file for file."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {}
+    for name, t in out.items():
+        if torch.is_tensor(t):
+            t = t.detach().cpu()
+            arrays[name] = t.numpy() if t.dtype == torch.float64 else t.float().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -784,12 +812,19 @@ def main():
     from mdfnet_hip.pipeline import DEFAULT_IN_FLIGHT
     ap.add_argument("--in-flight", type=int, default=int(os.environ.get("MDF_BENCH_IN_FLIGHT", DEFAULT_IN_FLIGHT)),
                     help="items in flight on that many HIP streams (the eval driver's pipelining); 1 = strictly one at a time")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: repeated timed blocks, the one-at-a-time view, the per-kernel profile pass "
+                         "and roofline, the training step, the cfg4 / cfg5_scan blocks and the CPU baseline (each --no-* option "
+                         "below drops one of them again); a plain run times exactly --steps steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed (depth, confidence) as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--blocks", type=int, default=0,
                     help="the K-step timed block is repeated this many times (each one barrier + synchronize bracketed); the "
-                         "MEDIAN block is reported, all of them and their spread under `blocks_ms_per_step`.  0 (default) = as many "
-                         "as it takes for >= 1 s of timed work in total, at least 3, at most 41 (the driver's --steps 20 is 0.08 s a block)")
+                         "MEDIAN block is reported, all of them and their spread under `blocks_ms_per_step`.  0 (default) = one "
+                         "block in a plain run; with --full as many as it takes for >= 1 s of timed work in total, at least 3, "
+                         "at most 41 (--steps 20 is 0.08 s a block)")
     ap.add_argument("--rank-timeout", type=float, default=1500.0,
                     help="self-launched multi-rank runs (plain `python bench.py --gpus N`): seconds after which all ranks are stopped")
     ap.add_argument("--no-training", action="store_true", help="skip the BASELINE configs[2] training-step block (N=1: one GPU's step; "
@@ -867,7 +902,7 @@ def main():
             one_step()
         pipe.drain()
         block_dts = []
-        n_blocks = args.blocks if args.blocks > 0 else 3
+        n_blocks = args.blocks if args.blocks > 0 else (3 if args.full else 1)
         bi = 0
         while bi < n_blocks:
             bi += 1
@@ -888,14 +923,16 @@ def main():
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
                 bdt = float(t.item())
             block_dts.append(bdt)
-            if args.blocks <= 0 and bi == 1:                 # auto: >= 1 s of timed work (every rank computes the same count from the max-over-ranks time)
+            if args.full and args.blocks <= 0 and bi == 1:   # auto: >= 1 s of timed work (every rank computes the same count from the max-over-ranks time)
                 n_blocks = min(41, max(3, int(math.ceil(1.0 / max(bdt, 1e-4)))) | 1)
         dt = sorted(block_dts)[len(block_dts) // 2]          # the median block
         args.blocks = len(block_dts) if args.blocks <= 0 else args.blocks      # the other legs (serial view, training) take 3
         out = last["out"]
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(out, args.dump_outputs)
         # the same K steps strictly one at a time (latency view of the same work), rank 0 only, outside the timed region
         dt_serial = None
-        if rank == 0 and args.in_flight > 1:
+        if rank == 0 and args.full and args.in_flight > 1:
             ser = []
             for _ in range(min(3, max(1, args.blocks))):
                 torch.cuda.synchronize()
@@ -908,24 +945,24 @@ def main():
     assert torch.isfinite(out["depth"]).all()
 
     kernels, cpu, prof_info, training = None, None, None, None
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and args.full and not args.no_profile:
         kernels, prof_info = profile_pass(model, inputs)
     extra = {}
-    if rank == 0 and world == 1 and not args.no_extra_configs:
+    if rank == 0 and world == 1 and args.full and not args.no_extra_configs:
         torch.cuda.empty_cache()
         extra["cfg4"] = cfg4_block(dev, args.in_flight)
         torch.cuda.empty_cache()
         extra["cfg5_scan"] = cfg5_scan_block(dev, args.in_flight)
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_training:
+    if rank == 0 and world == 1 and args.full and not args.no_training:
         training = training_block(dev, args.train_steps, min(3, max(1, args.blocks)), args.train_stock_steps)
         if not args.no_train_graph:
             training["graph_replay"] = training_graph(args.train_steps, min(3, max(1, args.blocks)))
         primary_training_figure(training)
-    if world > 1 and not args.no_training:
+    if world > 1 and args.full and not args.no_training:
         barrier()                      # rank 0's profile pass is over: every rank enters the training leg together
         training = training_ddp_block(dev, world, rank, args.train_steps, min(3, max(1, args.blocks)))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline()
     if rank == 0:
         views_per_s = world * args.steps / dt

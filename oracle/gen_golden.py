@@ -273,6 +273,72 @@ def gen_io():
     print("io.npz written", raw.size, "bytes of PFM")
 
 
+LOADER_DTU_ITEMS = (0, 5, 13, -1)       # item indices read from each loader (negative: from the end), robust off and on
+LOADER_BLENDED_ITEMS = (0, 3, -1)
+
+
+def array_digest(a):
+    """dtype, shape and SHA-256 of an array's bytes: what train_loaders.npz keeps of the images and ground-truth maps (exact equality
+    at a few bytes per array)."""
+    import hashlib
+    a = np.ascontiguousarray(a)
+    return "%s|%s|%s" % (a.dtype.str, "x".join(str(n) for n in a.shape), hashlib.sha256(a.tobytes()).hexdigest())
+
+
+def loader_sets(root):
+    """The two small synthetic training sets (DTU and BlendedMVS layout, written by load/synthetic.py from fixed seeds) that
+    train_loaders.npz was read from -> (dtu root, dtu pair file, blendedmvs root)."""
+    from load import synthetic
+    droot = synthetic.write_dtu_train_set(os.path.join(root, "dtu"), scenes=(2, 6), nviews_total=6, lightings=(0, 3), width=96, height=64)
+    broot = synthetic.write_blendedmvs_set(os.path.join(root, "bl"), scans=("scanA", "scanB"), nviews_total=5, width=96, height=64)
+    return droot, os.path.join(droot, "Cameras", "pair.txt"), broot
+
+
+def gen_loaders():
+    """Items of the reference's own load/dtutrain.py and load/blendedtrain.py on loader_sets(): composition order, robust sampling
+    under random.seed(11), padding, ranges.  OpenCV is absent here, so the reference runs (in a subprocess, its `load` package
+    would shadow ours) with a stub `cv2` whose `resize` is our data_io.resize_nearest -- the nearest-resize itself is not part of
+    this fixture (tests/test_train_data_cpu.py pins it by its formula).  Cameras, ranges and lengths are stored as arrays, the images and
+    ground-truth maps as array_digest() strings."""
+    import inspect
+    import subprocess
+    import tempfile
+    from tools import data_io
+    with tempfile.TemporaryDirectory() as d:
+        droot, pair, broot = loader_sets(d)
+        stub = os.path.join(d, "stub")
+        os.makedirs(stub)
+        with open(os.path.join(stub, "cv2.py"), "w") as f:
+            f.write("import importlib.util\n"
+                    "_s = importlib.util.spec_from_file_location('_mdf_data_io', %r); _m = importlib.util.module_from_spec(_s); "
+                    "_s.loader.exec_module(_m)\n"
+                    "INTER_NEAREST = 0\n"
+                    "def resize(img, size, interpolation=None):\n"
+                    "    assert interpolation == INTER_NEAREST\n"
+                    "    return _m.resize_nearest(img, size)\n" % os.path.abspath(data_io.__file__))
+        code = inspect.getsource(array_digest) + (
+            "import sys, random, numpy as np; sys.path[:0] = [%r, %r]\n"
+            "from load.dtutrain import LoadDataset as D\n"
+            "from load.blendedtrain import LoadDataset as B\n"
+            "res = {}\n"
+            "def put(tag, it):\n"
+            "    for k in ('intrinsics', 'extrinsics', 'depth_range'): res[tag + k] = np.asarray(it[k])\n"
+            "    res[tag + 'imgs'] = np.array(array_digest(np.asarray(it['imgs'])))\n"
+            "    for k, v in it['ref_depths'].items(): res[tag + 'gt' + k] = np.array(array_digest(v))\n"
+            "for robust in (0, 1):\n"
+            "    d = D(%r, %r, [2, 6], [0, 3], 3, bool(robust)); b = B(%r, 4, bool(robust))\n"
+            "    res['len_d%%d' %% robust] = np.array(len(d)); res['len_b%%d' %% robust] = np.array(len(b))\n"
+            "    random.seed(11)\n"
+            "    for i in %r: put('d%%d_%%d_' %% (robust, i), d[i %% len(d)])\n"
+            "    for i in %r: put('b%%d_%%d_' %% (robust, i), b[i %% len(b)])\n"
+            "np.savez_compressed(%r, **res)\n"
+            % (REF, stub, droot, pair, broot, LOADER_DTU_ITEMS, LOADER_BLENDED_ITEMS, os.path.join(OUT, "train_loaders.npz")))
+        env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
+        env.pop("PYTHONPATH", None)
+        subprocess.run([sys.executable, "-c", code], check=True, env=env, cwd=d)
+    print("train_loaders.npz written")
+
+
 def filter_scene(h=96, w=128, nsrc=10, seed=3):
     """Synthetic multi-view depth maps of a slanted plane + bumps, with per-view noise/outliers, DTU-like cameras.
     Returns float32 numpy arrays: depths [V,h,w], conf [h,w], K [V,3,3], E [V,4,4] (view 0 = reference)."""
@@ -345,6 +411,8 @@ def main():
         return gen_io()
     if "--only-filter" in sys.argv:
         return gen_filter()
+    if "--only-loaders" in sys.argv:
+        return gen_loaders()
     cfg, base, agg, regress, dh, scale, ref_loss = load_reference()
     model = cfg.model
     sd = synth.seeded_state_dict(model.state_dict(), seed=1)
@@ -468,6 +536,7 @@ def main():
     gen_train_f64(model, ref_loss, sd)
     gen_io()
     gen_filter()
+    gen_loaders()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)) // 1024, "KiB")
 

@@ -20,6 +20,6 @@ rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/r5_pmc_t_fetch -- p
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/r5_pmc_t_write -- python3 scripts/bench_train.py > gpurun_out/r5_pmc_t_write.log 2>&1
 echo train pmc done
 unset MDF_TRAIN_STAGE_STREAMS
-python3 bench.py --steps 20 --warmup 3 > gpurun_out/r5_bench_cfg2.json 2> gpurun_out/r5_bench_cfg2.err
+python3 bench.py --full --steps 20 --warmup 3 > profiles/r05_bench_cfg2.json
 MDF_TRAIN_GRAPH=1 MDF_TRAIN_PIECES=1 MDF_TRAIN_STEPS=30 python3 scripts/bench_train.py > gpurun_out/r5_train_pieces.log 2>&1
 echo profiles done

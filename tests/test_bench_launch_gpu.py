@@ -1,4 +1,4 @@
-"""GPU: `python bench.py --gpus 2` (no torchrun environment) starts two ranks itself and reports n_gpus = 2.  Rehearsed on the
+"""GPU: `python bench.py --gpus 2 --full` (no torchrun environment) starts two ranks itself and reports n_gpus = 2.  Rehearsed on the
 one-GPU box with both ranks sharing the card and gloo for the barrier/max-over-ranks (MDF_BENCH_SHARE_GPU, MDF_BENCH_DIST_BACKEND),
 at a reduced size so that it takes seconds."""
 import json
@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_self_launches_two_ranks():
     env = dict(os.environ, MDF_BENCH_SHARE_GPU="1", MDF_BENCH_DIST_BACKEND="gloo", MDF_BENCH_SIZE="320x256x5")
     env.pop("WORLD_SIZE", None), env.pop("RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
                         "--no-cpu-baseline", "--no-profile", "--train-steps", "2", "--blocks", "1"], capture_output=True, text=True,
                        timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -31,6 +31,27 @@ def test_bench_self_launches_two_ranks():
     assert tr["samples_per_s"] == tr["allreduce"]["samples_per_s"]
     assert "direct" in tr and ("ms_per_step" in tr["direct"] or "error" in tr["direct"])
     assert "cfg4" not in rec and "cfg5_scan" not in rec            # N = 1 blocks only
+
+
+def test_bench_plain_run_times_the_headline_only_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps in one block, prints the headline keys and nothing that needs a pass of
+    its own, and --dump-outputs writes the last step's depth / confidence as float32 .npy."""
+    import numpy as np
+    env = dict(os.environ, MDF_BENCH_SIZE="320x256x5")
+    env.pop("WORLD_SIZE", None), env.pop("RANK", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in rec, k
+    assert rec["steps"] == 4 and rec["value"] > 0 and rec["ms_per_step"] > 0 and len(rec["blocks_ms_per_step"]["all"]) == 1
+    assert abs(rec["value"] - 1e3 / rec["ms_per_step"]) <= 1e-2 * rec["value"]
+    for k in ("roofline", "kernels", "training", "cfg4", "cfg5_scan", "cpu_baseline", "one_at_a_time"):
+        assert k not in rec, k
+    for name in ("depth", "confidence"):
+        a = np.load(str(tmp_path / "out" / (name + ".npy")))
+        assert a.dtype == np.float32 and a.shape == (1, 256, 320) and np.isfinite(a).all(), name
 
 
 def test_bench_extra_config_blocks_at_reduced_size():

@@ -1,5 +1,5 @@
-"""CPU: the product's `net` package is a drop-in for the reference's (same state_dict contract), and — when the
-reference tree is present (build container only) — the reference's own config.py composes its model out of OUR slots."""
+"""CPU: the product's `net` package is a drop-in for the reference's (same state_dict contract), and a reference-layout
+config.py composes its model out of OUR slots when mdfnet_hip.dropin is installed in front of it."""
 import os
 import subprocess
 import sys
@@ -9,7 +9,6 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.environ.get("MDF_REFERENCE", "/root/reference")
 
 
 def test_state_dict_matches_reference_contract(golden, seeded_sd):
@@ -46,12 +45,35 @@ def test_slot_signatures_and_mode_dispatch(rehearsal_backend):
         m.Homoaggre[0]([torch.zeros(1, 64, 4, 4)] * 2, rp, sps[:1], hyp)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "config.py")), reason="reference tree not present (GPU box)")
-def test_reference_config_builds_on_our_slots():
+# A reference-layout tree: a `config.py` that composes the model out of the `net` slots the way the reference's config.py:186-218
+# does (the public constructor contract: FPN_4Scales(chs), HyposByFit(ndepths, curve, prob_thresh), VectorAggregate(ngroups), the
+# 3-scale / 4-scale regularisers, the two regression functions, RefineNet2), next to a `net/` package of its own that must never be
+# imported -- in the reference tree it is the CUDA-era package the drop-in replaces.
+STAND_IN_CONFIG = """\
+import torch.nn as nn
+from net import core
+from net.unit import scale, backbone, regress, refine
+from net.unit.depthhypos import HyposByFit
+from net.unit.homoaggregate import VectorAggregate
+from net.unit.regular import RegularNet_4Scales, RegularNet_3Scales
+hypos = nn.ModuleList([HyposByFit(n, c, t) for n, c, t in zip((48, 24, 8), (None, "gauss1", "laplace"), (0.0, 0.95, 1e-5))])
+aggregate = nn.ModuleList([VectorAggregate(g) for g in (32, 16, 8)])
+regular = nn.ModuleList([RegularNet_3Scales(32), RegularNet_4Scales(16), RegularNet_4Scales(8)])
+model = core.CoreNet(backbone.FPN_4Scales((8, 16, 32, 64)), hypos, scale.scale_cam, aggregate, regular,
+                     [regress.depth_regression, regress.confidence_regress], refine.RefineNet2())
+"""
+
+
+def test_reference_config_builds_on_our_slots(tmp_path):
+    ref = tmp_path / "reference"
+    (ref / "net" / "unit").mkdir(parents=True)
+    (ref / "config.py").write_text(STAND_IN_CONFIG)
+    for f in ("net/__init__.py", "net/core.py", "net/unit/__init__.py"):
+        (ref / f).write_text("raise ImportError('the reference tree\\'s own net package was imported')\n")
     code = (
         "import sys, io, contextlib; sys.path.insert(0, %r)\n"
         "from mdfnet_hip import dropin; dropin.install(%r)\n"
-        "import os; os.chdir('/tmp')\n"
+        "import os; os.chdir(%r)\n"
         "with contextlib.redirect_stdout(io.StringIO()):\n"
         "    import config\n"
         "import net.core, net.unit.regular\n"
@@ -61,7 +83,7 @@ def test_reference_config_builds_on_our_slots():
         "assert type(m).__module__ == 'net.core' and type(m.Regular[0]).__module__ == 'net.unit.regular'\n"
         "from mdfnet_hip import ops  # our slots are HIP-backed\n"
         "print(len(m.state_dict()), sum(p.numel() for p in m.parameters()))\n"
-    ) % (os.path.join(ROOT, "mdf-net_amd"), REF, REF, os.path.join(ROOT, "mdf-net_amd"))
+    ) % (os.path.join(ROOT, "mdf-net_amd"), str(ref), str(tmp_path), str(ref), os.path.join(ROOT, "mdf-net_amd"))
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True,
                        env={**os.environ, "PYTHONDONTWRITEBYTECODE": "1"})
     assert r.returncode == 0, r.stderr[-2000:]

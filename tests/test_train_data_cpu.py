@@ -5,7 +5,6 @@ import os
 import random
 
 import numpy as np
-import pytest
 import torch
 
 from load import synthetic
@@ -100,66 +99,34 @@ def test_one_training_epoch_on_the_synthetic_dtu_train_set(tmp_path, monkeypatch
     m2.load_state_dict(torch.load(ck, map_location="cpu")["model"])          # train.py:60-68 checkpoint format, strict
 
 
-REF = os.environ.get("MDF_REFERENCE", "/root/reference")
-
-
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "load", "dtutrain.py")), reason="reference tree not present (GPU box)")
-def test_loaders_match_the_reference_loaders_item_for_item(tmp_path):
-    """Build container only: the reference's own load/dtutrain.py and load/blendedtrain.py, run in a subprocess on the same
-    synthetic sets, return the same items (composition order, robust sampling under the same `random` seed, padding, ranges).
-    OpenCV is absent here, so the subprocess gets a stub `cv2` whose `resize` is data_io.resize_nearest -- the nearest-resize
-    itself is therefore NOT part of this comparison (it is pinned by its formula in the first test)."""
-    import subprocess
-    import sys
-    droot = synthetic.write_dtu_train_set(str(tmp_path / "dtu"), scenes=(2, 6), nviews_total=6, lightings=(0, 3), width=96, height=64)
-    broot = synthetic.write_blendedmvs_set(str(tmp_path / "bl"), scans=("scanA", "scanB"), nviews_total=5, width=96, height=64)
-    stub = tmp_path / "stub"
-    stub.mkdir()
-    ours = os.path.join(os.path.dirname(data_io.__file__), "data_io.py")
-    (stub / "cv2.py").write_text(
-        "import importlib.util\n"
-        "_s = importlib.util.spec_from_file_location('_mdf_data_io', %r); _m = importlib.util.module_from_spec(_s); _s.loader.exec_module(_m)\n"
-        "INTER_NEAREST = 0\n"
-        "def resize(img, size, interpolation=None):\n"
-        "    assert interpolation == INTER_NEAREST\n"
-        "    return _m.resize_nearest(img, size)\n" % ours)
-    out = str(tmp_path / "ref_items.npz")
-    code = (
-        "import sys, random, numpy as np; sys.path[:0] = [%r, %r]\n"
-        "import os; os.chdir('/tmp')\n"
-        "from load.dtutrain import LoadDataset as D\n"
-        "from load.blendedtrain import LoadDataset as B\n"
-        "res = {}\n"
-        "def put(tag, it):\n"
-        "    for k in ('imgs', 'intrinsics', 'extrinsics', 'depth_range'): res[tag + k] = np.asarray(it[k])\n"
-        "    for k, v in it['ref_depths'].items(): res[tag + 'gt' + k] = v\n"
-        "for robust in (0, 1):\n"
-        "    d = D(%r, %r, [2, 6], [0, 3], 3, bool(robust)); b = B(%r, 4, bool(robust))\n"
-        "    res['len_d%%d' %% robust] = np.array(len(d)); res['len_b%%d' %% robust] = np.array(len(b))\n"
-        "    random.seed(11)\n"
-        "    for i in (0, 5, 13, len(d) - 1): put('d%%d_%%d_' %% (robust, i), d[i])\n"
-        "    for i in (0, 3, len(b) - 1): put('b%%d_%%d_' %% (robust, i), b[i])\n"
-        "np.savez(%r, **res)\n" % (REF, str(stub), droot, os.path.join(droot, "Cameras", "pair.txt"), broot, out))
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    env.pop("PYTHONPATH", None)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref = np.load(out)
+def test_loaders_match_the_reference_loaders_item_for_item(tmp_path, golden):
+    """The reference's own load/dtutrain.py and load/blendedtrain.py, run on the same synthetic sets, returned the items stored in
+    tests/golden/train_loaders.npz (oracle/gen_golden.py:gen_loaders; images and ground-truth maps by dtype, shape and SHA-256); ours
+    return the same items (composition order, robust sampling
+    under the same `random` seed, padding, ranges).  OpenCV was absent there, so the reference ran with a stub `cv2` whose `resize`
+    is data_io.resize_nearest -- the nearest-resize itself is therefore NOT part of this comparison (it is pinned by its formula in
+    the first test)."""
+    from oracle import gen_golden
+    ref = golden("train_loaders.npz")
+    droot, pair, broot = gen_golden.loader_sets(str(tmp_path))
     from load.blendedtrain import LoadDataset as B
     from load.dtutrain import LoadDataset as D
     n = 0
     for robust in (0, 1):
-        d = D(droot, os.path.join(droot, "Cameras", "pair.txt"), [2, 6], [0, 3], 3, bool(robust))
+        d = D(droot, pair, [2, 6], [0, 3], 3, bool(robust))
         b = B(broot, 4, bool(robust))
         assert len(d) == int(ref["len_d%d" % robust]) and len(b) == int(ref["len_b%d" % robust])
         random.seed(11)
-        items = [("d%d_%d_" % (robust, i), d[i]) for i in (0, 5, 13, len(d) - 1)] + [("b%d_%d_" % (robust, i), b[i]) for i in (0, 3, len(b) - 1)]
+        items = ([("d%d_%d_" % (robust, i), d[i % len(d)]) for i in gen_golden.LOADER_DTU_ITEMS] +
+                 [("b%d_%d_" % (robust, i), b[i % len(b)]) for i in gen_golden.LOADER_BLENDED_ITEMS])
         for tag, it in items:
-            for k in ("imgs", "intrinsics", "extrinsics", "depth_range"):
+            for k in ("intrinsics", "extrinsics", "depth_range"):
                 a = np.asarray(it[k])
                 assert a.dtype == ref[tag + k].dtype and np.array_equal(a, ref[tag + k]), tag + k
+            assert gen_golden.array_digest(np.asarray(it["imgs"])) == str(ref[tag + "imgs"]), tag + "imgs"
+            assert sorted("gt" + k for k in it["ref_depths"]) == sorted(k[len(tag):] for k in ref if k.startswith(tag + "gt")), tag
             for k, v in it["ref_depths"].items():
-                assert np.array_equal(v, ref[tag + "gt" + k]), tag + k
+                assert gen_golden.array_digest(v) == str(ref[tag + "gt" + k]), tag + k
             n += 1
     assert n == 14
 
