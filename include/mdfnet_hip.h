@@ -40,6 +40,7 @@ extern "C" {
 #define MDF_VOL_NDHWC 1
 
 #define MDF_MAX_SRC_VIEWS 16
+#define MDF_MAX_FUSE_VIEWS 1024   /* views of one scan in mdf_consensus_fuse_fwd's camera table */
 
 int mdf_abi_version(void);
 const char* mdf_last_error(void);
@@ -222,6 +223,30 @@ int mdf_hypos_from_fit_fwd(int mode, const float* s, const float* depth, const f
 int mdf_consistency_fuse_fwd(const float* depth_ref, const float* conf, const float* const* src_depths, const float* mats,
                              int n_src, int h, int w, float photo_threshold, int nconditions, float thre1, float thre2,
                              float* depth_avg, unsigned char* masks, unsigned short* view_masks, float* rep_out, void* stream);
+
+/* ---- DTU depth-map fusion by multi-view consensus (tools/gipuma/main.py -d -> fusibile, fusibile.cu:138-276 with
+ *      normal_thresh 360 and view selection off) ----------------------------------------------------------------------
+ * One call per scan: every view is the reference view once, every other view of the scan is checked.  For pixel (x, y) of
+ * view r with depth d: X = M_inv_r (d*x - p4.x, d*y - p4.y, d - p4.z); for each v != r project X with P_v to (u, w, z),
+ * pt = (u/z, w/z), skip v unless 0 <= pt < (w, h); sample v's depth bilinearly at pt (wrap addressing, exact fp32 weights)
+ * -> d^; v agrees when |f*b/z - f*b/d^| < disp_thresh with b = |C_r - C_v|; an agreeing view adds
+ * M_inv_v (d^*floor(pt.x) - p4.x, d^*floor(pt.y) - p4.y, d^ - p4.z) and its bilinear colour to the sums.  A point is kept when
+ * n >= num_consistent and none of its averaged coordinates is exactly 0; a non-finite point is written as (0,0,0).
+ * Output order: reference view, then row-major pixel (order-preserving compaction, no atomics).
+ *   depths [n,h,w] fp32 (0 = invalid); colors [n,h,w,4] uint8 (R,G,B,unused; 4-byte aligned)
+ *   cams [n][32] fp32 per view: P [3x4 row-major], M_inv = inv(P[:, :3]) [9], centre C = -M_inv P[:, 3] [3], 8 unused
+ *   f: the focal length of the scan's first camera, used for every view
+ *   workspace: mdf_consensus_fuse_workspace(n, h, w) bytes, 16-byte aligned
+ *   xyz [capacity,3] fp32, rgb [capacity,3] uint8 (points past capacity are not written), or both NULL: then only the fusion
+ *   and the count scan run, and mdf_consensus_compact writes the points from the same workspace once the caller has read
+ *   *total and sized the output (what ops.consensus_fuse does: the output holds exactly the kept points);
+ *   view_counts [n] int32 points kept per reference view; total [1] int64 points kept (may exceed capacity)
+ * Device memory: the workspace is 16 B per (view, pixel) (+ 12 B per 256-pixel block): 1.5 GB for 49 x 1600 x 1184.       */
+long long mdf_consensus_fuse_workspace(int n, int h, int w);
+int mdf_consensus_fuse_fwd(const float* depths, const unsigned char* colors, const float* cams, int n, int h, int w, float f,
+                           float disp_thresh, int num_consistent, void* workspace, float* xyz, unsigned char* rgb,
+                           long long capacity, int* view_counts, long long* total, void* stream);
+int mdf_consensus_compact(void* workspace, int n, int h, int w, float* xyz, unsigned char* rgb, long long capacity, void* stream);
 
 /* =====================================================================================================
  * Training path (BASELINE config 3; train.py:36-45 -> loss.backward()).  The reference has no explicit backward:

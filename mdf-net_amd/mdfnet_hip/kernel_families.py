@@ -44,6 +44,8 @@ KERNEL_FAMILY = {
     "hypos_fit_kernel": HEADS, "hypos_from_fit_kernel": HEADS, "refine_head_kernel": HEADS, "fpn_compose_fwd_kernel": HEADS, "fpn_compose_bwd_kernel": HEADS,
     # consistency.hip
     "consistency_fuse_kernel": FILTER,
+    # consensus_fuse.hip (DTU fusion: the gipuma / fusibile step)
+    "consensus_fuse_kernel": FILTER, "consensus_scan_kernel": FILTER, "consensus_compact_kernel": FILTER,
     # loss.hip
     "masked_smooth_l1_reduce_kernel": CONTROL, "masked_smooth_l1_finalize_kernel": CONTROL, "masked_smooth_l1_bwd_kernel": CONTROL,
     "masked_smooth_l1_reduce_multi_kernel": CONTROL, "masked_smooth_l1_bwd_multi_kernel": CONTROL, "adam_step_kernel": CONTROL,

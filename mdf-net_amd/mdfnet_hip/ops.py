@@ -675,3 +675,59 @@ def consistency_fuse(depth_ref, conf, k_ref, e_ref, src_depths, src_ks, src_es, 
         out["view_masks"] = torch.stack([((bits >> i) & 1).bool() for i in range(9)], dim=1)
         out["rep"] = rep
     return out
+
+
+# --------------------------------------------------------------------------- DTU fusion: multi-view consensus (gipuma / fusibile)
+CONSENSUS_CAM_STRIDE = 32
+
+
+def consensus_cameras(K, E):
+    """HOST: the camera table of mdf_consensus_fuse_fwd from intrinsics K [N,3,3] and extrinsics E [N,4,4] (any array-like).
+    P = K E[:3] in float64 rounded to fp32 (what the reference writes as text and fusibile reads back as float);
+    M_inv = inv(P[:, :3]) and C = -M_inv P[:, 3] in float64 from that fp32 P, rounded to fp32.  f = K[0][0, 0] of the scan's FIRST
+    camera, used for every view.  -> (table [N, 32] float32 numpy, f float32)."""
+    import numpy as np
+    K = np.asarray(K, dtype=np.float32).astype(np.float64)
+    E = np.asarray(E, dtype=np.float32).astype(np.float64)
+    n = K.shape[0]
+    tab = np.zeros((n, CONSENSUS_CAM_STRIDE), dtype=np.float32)
+    for v in range(n):
+        P = (K[v] @ E[v][:3]).astype(np.float32)
+        m_inv = np.linalg.inv(P[:, :3].astype(np.float64))
+        tab[v, 0:12] = P.reshape(-1)
+        tab[v, 12:21] = m_inv.astype(np.float32).reshape(-1)
+        tab[v, 21:24] = (-(m_inv @ P[:, 3].astype(np.float64))).astype(np.float32)
+    return tab, np.float32(K[0][0, 0])
+
+
+def consensus_fuse(depths, images, K, E, disp_thresh, num_consistent):
+    """Fuse one scan's depth maps into a point cloud (the reference's DTU protocol: tools/gipuma/main.py -d).
+    depths: GPU fp32 [N,H,W] (0 = invalid; apply the probability filter first); images: GPU uint8 [N,H,W,3] RGB;
+    K [N,3,3], E [N,4,4]: host arrays.  -> (xyz [M,3] fp32, rgb [M,3] uint8, per-view kept counts [N] int32), all on the GPU,
+    points in reference-view then row-major pixel order.  Device memory beyond the inputs: a workspace of 16 B per (view, pixel)
+    (1.5 GB for a 49 x 1600 x 1184 DTU scan, ~16 GB for a 509-view Tanks scan at 1920 x 1056) plus 15 B per kept point."""
+    _need_gpu(depths, images)
+    if depths.dim() != 3 or images.dim() != 4 or tuple(images.shape) != (*depths.shape, 3) or images.dtype != torch.uint8:
+        raise ValueError(f"depths [N,H,W] fp32 and images [N,H,W,3] uint8 expected, got {tuple(depths.shape)} and "
+                         f"{tuple(images.shape)} {images.dtype}")
+    n, h, w = depths.shape
+    dev = depths.device
+    tab, f = consensus_cameras(K, E)
+    cams = torch.from_numpy(tab).to(dev)
+    colors = torch.nn.functional.pad(images, (0, 1)).contiguous()          # RGBA8: one 4-byte gather per texel
+    depths = _f32c(depths)
+    ws = torch.empty(int(lib().mdf_consensus_fuse_workspace(n, h, w)), device=dev, dtype=torch.uint8)
+    counts = torch.empty(n, device=dev, dtype=torch.int32)
+    total = torch.empty(1, device=dev, dtype=torch.int64)
+    # two phases: fusion + count scan, then (the kept total read back) the compaction into outputs of exactly that size
+    _abi("mdf_consensus_fuse_fwd", (depths.data_ptr(), colors.data_ptr(), cams.data_ptr(), n, h, w, ctypes.c_float(float(f)),
+                                    ctypes.c_float(disp_thresh), int(num_consistent), ws.data_ptr(), None, None, 0,
+                                    counts.data_ptr(), total.data_ptr(), _stream(depths)),
+         tag=f"{w}x{h} n{n}", work={"pairs": float(n) * (n - 1) * h * w, "bound": "valu"})
+    m = int(total.item())
+    xyz = torch.empty((m, 3), device=dev, dtype=torch.float32)
+    rgb = torch.empty((m, 3), device=dev, dtype=torch.uint8)
+    if m:
+        _abi("mdf_consensus_compact", (ws.data_ptr(), n, h, w, xyz.data_ptr(), rgb.data_ptr(), m, _stream(depths)),
+             tag=f"{w}x{h} n{n}", work={"bytes": 16.0 * n * h * w + 15.0 * m, "bound": "hbm"})
+    return xyz, rgb, counts

@@ -88,6 +88,33 @@ def read_img(filename):
     return np.array(Image.open(filename), dtype=np.float32) / 255.0
 
 
+def write_ply(path, xyz, rgb):
+    """Vertices with float x,y,z (15 bytes each) + uchar red,green,blue; binary_little_endian 1.0 (what PlyData([el]).write produces)."""
+    xyz = np.asarray(xyz, dtype="<f4").reshape(-1, 3)
+    rgb = np.asarray(rgb, dtype=np.uint8).reshape(-1, 3)
+    rec = np.empty(len(xyz), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    rec["x"], rec["y"], rec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    rec["red"], rec["green"], rec["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % len(rec))
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        rec.tofile(f)
+
+
+def read_ply(path):
+    with open(path, "rb") as f:
+        n = None
+        while True:
+            line = f.readline().decode("ascii").strip()
+            if line.startswith("element vertex"):
+                n = int(line.split()[-1])
+            if line == "end_header":
+                break
+        rec = np.fromfile(f, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")], count=n)
+    return np.stack([rec["x"], rec["y"], rec["z"]], 1), np.stack([rec["red"], rec["green"], rec["blue"]], 1)
+
+
 def tocuda(data_batch, device, parallel=False):
     out = {}
     for k, v in data_batch.items():
