@@ -248,6 +248,42 @@ int mdf_consensus_fuse_fwd(const float* depths, const unsigned char* colors, con
                            long long capacity, int* view_counts, long long* total, void* stream);
 int mdf_consensus_compact(void* workspace, int n, int h, int w, float* xyz, unsigned char* rgb, long long capacity, void* stream);
 
+/* ---- Point-cloud fusion with visibility and small-segment filters (tools/pcd/fusion.py:get_cloud, stages 2-6; the two C++
+ *      cores of tools/pcd/utils/fusion.cpp) ---------------------------------------------------------------------------
+ * One call per scan runs steps first_step..last_step of the pipeline over every view (each step computes every view's update
+ * from the state before the step, then applies all updates), in place on depths / masks:
+ *   MDF_PCD_STEP_VIS1/2/3  visibility filter (get_reproj + vis_filter, img_dist 1, depth_thresh 0.01): a pixel stays when at
+ *                          least `need` of its sources reproject within 1 px and 1 % depth; depth *= mask
+ *   MDF_PCD_STEP_FUSION    visibility fusion (vis_fusion + vis_fusion_core): per pixel bin, the first (depth, violations)-sorted
+ *                          candidate k with k >= violations[k], else the last; depth = fused * mask
+ *   MDF_PCD_STEP_AVE       average fusion: (sum_v reproj_d * mask_v + d) / (sum_v mask_v + 1); depth = ave * mask
+ *   MDF_PCD_STEP_SEG       small-segment filter (small_seg_core(depth, 4, 1e-3, 10)): 9x9-window components of < 10 pixels
+ *                          are dropped; mask &= seg; depth *= mask
+ * then counts the mask-true pixels: view_counts [n] int32, total [1] int64.  mdf_pcd_compact then writes the points of the
+ * mask-true pixels (lifted at pixel centres), their colours and the direction to the camera centre, in view then row-major
+ * order (ordered compaction, no atomics), from the same workspace and the unchanged depths / masks.
+ *   depths [n,h,w] fp32, masks [n,h,w] uint8 (0/1); rgb [n,h,w,3] uint8
+ *   cams [n][64] fp32 per view: K [9], K^-1 [9], E [16], E^-1 [16], centre -R^T t [3] (K^-1, E^-1, centre in float64 from the
+ *   fp32 K, E, rounded to fp32), 11 unused
+ *   srcs [n][v] int32 source views of each view (-1 = none; an entry outside [0, n) is treated as none); v <= MDF_PCD_MAX_SOURCES;
+ *   need = ceil(fp32(vthresh - 1.1))
+ *   workspace: mdf_pcd_fuse_workspace(n, h, w, v) bytes, 16-byte aligned: 13 B per (view, pixel) + 8 (v + 3) B per pixel
+ *   of one view (1.77 GiB for 64 x 1056 x 1920 with 10 sources)
+ *   xyz, dirs [capacity,3] fp32, rgb_out [capacity,3] uint8 (points past capacity are not written)                        */
+#define MDF_PCD_MAX_SOURCES 64
+#define MDF_PCD_STEP_VIS1 1
+#define MDF_PCD_STEP_FUSION 2
+#define MDF_PCD_STEP_VIS2 3
+#define MDF_PCD_STEP_AVE 4
+#define MDF_PCD_STEP_VIS3 5
+#define MDF_PCD_STEP_SEG 6
+long long mdf_pcd_fuse_workspace(int n, int h, int w, int v);
+int mdf_pcd_fuse_fwd(float* depths, unsigned char* masks, const float* cams, const int* srcs, int n, int h, int w, int v, int need,
+                     int first_step, int last_step, void* workspace, int* view_counts, long long* total, void* stream);
+int mdf_pcd_compact(const float* depths, const unsigned char* masks, const unsigned char* rgb, const float* cams, int n, int h,
+                    int w, int v, void* workspace, float* xyz, unsigned char* rgb_out, float* dirs, long long capacity,
+                    void* stream);
+
 /* =====================================================================================================
  * Training path (BASELINE config 3; train.py:36-45 -> loss.backward()).  The reference has no explicit backward:
  * autograd differentiates the op chains cited above.  Each entry below is the hand-written forward-in-train-mode or

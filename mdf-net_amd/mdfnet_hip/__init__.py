@@ -61,6 +61,9 @@ SIGNATURES = {
     "mdf_consensus_fuse_fwd": (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, c_int, c_fp, c_fp, c_fp,
                                        c_i64, c_fp, c_fp, c_fp]),
     "mdf_consensus_compact": (c_int, [c_fp, c_int, c_int, c_int, c_fp, c_fp, c_i64, c_fp]),
+    "mdf_pcd_fuse_workspace": (c_i64, [c_int, c_int, c_int, c_int]),
+    "mdf_pcd_fuse_fwd": (c_int, [c_fp, c_fp, c_fp, c_fp] + [c_int] * 7 + [c_fp, c_fp, c_fp, c_fp]),
+    "mdf_pcd_compact": (c_int, [c_fp, c_fp, c_fp, c_fp] + [c_int] * 4 + [c_fp, c_fp, c_fp, c_fp, c_i64, c_fp]),
     "mdf_bn_stats_fwd": (c_int, [c_fp, c_i64, c_int, c_int, c_fp, c_fp]),
     "mdf_bn_finalize_fwd": (c_int, [c_fp, c_fp, c_fp, ctypes.c_float, ctypes.c_float, c_i64, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_fp]),
     "mdf_bn_relu_apply_fwd": (c_int, [c_fp, c_fp, c_fp, c_fp, c_i64, c_int, c_int, c_fp]),
@@ -135,3 +138,9 @@ def check(rc, what):
     if rc != 0:
         msg = lib().mdf_last_error().decode("utf-8", "replace")
         raise MdfHipError(f"{what} failed with code {rc}: {msg}")
+
+
+def pcd_fuse(*args, **kwargs):
+    """Point-cloud fusion of one scan (ops.pcd_fuse; the reference's tools/pcd/fusion.py:get_cloud)."""
+    from .ops import pcd_fuse as _pcd_fuse
+    return _pcd_fuse(*args, **kwargs)

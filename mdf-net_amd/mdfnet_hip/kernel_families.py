@@ -46,6 +46,10 @@ KERNEL_FAMILY = {
     "consistency_fuse_kernel": FILTER,
     # consensus_fuse.hip (DTU fusion: the gipuma / fusibile step)
     "consensus_fuse_kernel": FILTER, "consensus_scan_kernel": FILTER, "consensus_compact_kernel": FILTER,
+    # pcd_fusion.hip (point-cloud fusion: the tools/pcd step)
+    "pcd_reproj_kernel": FILTER, "pcd_cand_count_kernel": FILTER, "pcd_cand_place_kernel": FILTER, "pcd_select_kernel": FILTER, "pcd_select_big_kernel": FILTER, "pcd_bin_sum_kernel": FILTER, "pcd_bin_offsets_kernel": FILTER,
+    "pcd_seg_init_kernel": FILTER, "pcd_seg_hook_kernel": FILTER, "pcd_seg_count_kernel": FILTER, "pcd_seg_apply_kernel": FILTER,
+    "pcd_count_kernel": FILTER, "pcd_scan_kernel": FILTER, "pcd_compact_kernel": FILTER,
     # loss.hip
     "masked_smooth_l1_reduce_kernel": CONTROL, "masked_smooth_l1_finalize_kernel": CONTROL, "masked_smooth_l1_bwd_kernel": CONTROL,
     "masked_smooth_l1_reduce_multi_kernel": CONTROL, "masked_smooth_l1_bwd_multi_kernel": CONTROL, "adam_step_kernel": CONTROL,

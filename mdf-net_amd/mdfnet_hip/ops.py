@@ -731,3 +731,106 @@ def consensus_fuse(depths, images, K, E, disp_thresh, num_consistent):
         _abi("mdf_consensus_compact", (ws.data_ptr(), n, h, w, xyz.data_ptr(), rgb.data_ptr(), m, _stream(depths)),
              tag=f"{w}x{h} n{n}", work={"bytes": 16.0 * n * h * w + 15.0 * m, "bound": "hbm"})
     return xyz, rgb, counts
+
+
+# --------------------------------------------------------------------------- point-cloud fusion (tools/pcd: visibility + small segments)
+PCD_CAM_STRIDE = 64
+PCD_STEPS = ("prob", "vis1", "vis_fusion", "vis2", "ave", "vis3", "seg")   # index k of a step == its MDF_PCD_STEP_* (prob: 0)
+PCD_MAX_SOURCES = 64
+PCD_PROB_THRESHOLD = 0.8
+
+
+def pcd_cameras(K, E):
+    """HOST: the camera table of mdf_pcd_fuse_fwd from intrinsics K [N,3,3] and extrinsics E [N,4,4] (any array-like):
+    K, K^-1, E, E^-1 and the camera centre -R^T t, the last three in float64 from the fp32 K and E, rounded to fp32.
+    -> float32 numpy [N, 64]."""
+    import numpy as np
+    K = np.asarray(K, dtype=np.float32)
+    E = np.asarray(E, dtype=np.float32)
+    tab = np.zeros((K.shape[0], PCD_CAM_STRIDE), dtype=np.float32)
+    for v in range(K.shape[0]):
+        k64, e64 = K[v].astype(np.float64), E[v].astype(np.float64)
+        tab[v, 0:9] = K[v].ravel()
+        tab[v, 9:18] = np.linalg.inv(k64).astype(np.float32).ravel()
+        tab[v, 18:34] = E[v].ravel()
+        tab[v, 34:50] = np.linalg.inv(e64).astype(np.float32).ravel()
+        tab[v, 50:53] = (-(e64[:3, :3].T @ e64[:3, 3])).astype(np.float32)
+    return tab
+
+
+def pcd_sources(src_table, n, view):
+    """HOST: [[source view indices of view i, best first] ...] (or an int array, -1 = none) -> int32 numpy [n, view]: the first
+    `view` entries of each list, padded with -1."""
+    import numpy as np
+    t = np.full((n, view), -1, dtype=np.int32)
+    for i in range(n):
+        s = [int(x) for x in list(src_table[i]) if int(x) >= 0][:view]
+        if any(x >= n for x in s):
+            raise ValueError(f"view {i}: source index out of range in {s}")
+        t[i, :len(s)] = s
+    return t
+
+
+def pcd_steps(depths, masks, cams, srcs, need, first, last):
+    """Steps first..last (1..6, see PCD_STEPS) of the fusion pipeline in place on depths [N,H,W] fp32 / masks [N,H,W] uint8
+    (GPU); cams [N,64] and srcs [N,V] int32 on the GPU.  -> (workspace, per-view mask-true counts [N] int32, total int)."""
+    n, h, w = depths.shape
+    v = srcs.shape[1]
+    dev = depths.device
+    ws = torch.empty(int(lib().mdf_pcd_fuse_workspace(n, h, w, v)), device=dev, dtype=torch.uint8)
+    counts = torch.empty(n, device=dev, dtype=torch.int32)
+    total = torch.empty(1, device=dev, dtype=torch.int64)
+    _abi("mdf_pcd_fuse_fwd", (depths.data_ptr(), masks.data_ptr(), cams.data_ptr(), srcs.data_ptr() if v else None, n, h, w, v,
+                              int(need), int(first), int(last), ws.data_ptr(), counts.data_ptr(), total.data_ptr(),
+                              _stream(depths)),
+         tag=f"{w}x{h} n{n} v{v} steps{first}-{last}", work={"candidates": float(n) * (v + 1) * h * w, "bound": "valu"})
+    return ws, counts, int(total.item())
+
+
+def pcd_fuse(depths, probs, images, K, E, src_table, view=10, vthresh=4, normals=False, downsample=None, stages=None):
+    """Fuse one scan's depth maps into a point cloud (the reference's tools/pcd/fusion.py:get_cloud, stages 1-6).
+    depths, probs: GPU fp32 [N,H,W]; images: GPU uint8 [N,H,W,3] RGB; K [N,3,3], E [N,4,4]: host arrays; src_table: per view
+    the list of its source view indices (pair.txt order, already restricted to views of the scan), of which the first `view`
+    are used.  stages: None runs the whole pipeline; k in 1..7 stops after step PCD_STEPS[k-1] and returns that state only.
+    -> dict(depths [N,H,W] fp32, masks [N,H,W] bool, counts [N] int32, and with the whole pipeline xyz [M,3] fp32,
+    rgb [M,3] uint8, dirs [M,3] fp32 (camera centre - point)), all on the GPU, points in view then row-major pixel order.
+    Device memory beyond the inputs: mdf_pcd_fuse_workspace (13 B per view-pixel + 8 (view + 3) B per pixel of one view)
+    plus 27 B per point.  Normal estimation and voxel downsampling are not available yet: normals=True or a downsample
+    raises."""
+    import numpy as np
+    if normals or downsample is not None:
+        raise NotImplementedError("pcd_fuse: normal estimation and voxel downsampling are not implemented; "
+                                  "call with normals=False, downsample=None")
+    _need_gpu(depths, probs, images)
+    if depths.dim() != 3 or tuple(probs.shape) != tuple(depths.shape) or tuple(images.shape) != (*depths.shape, 3) \
+            or images.dtype != torch.uint8:
+        raise ValueError(f"depths / probs [N,H,W] fp32 and images [N,H,W,3] uint8 expected, got {tuple(depths.shape)}, "
+                         f"{tuple(probs.shape)} and {tuple(images.shape)} {images.dtype}")
+    if not 0 <= view <= PCD_MAX_SOURCES:
+        raise ValueError(f"view={view} out of range [0, {PCD_MAX_SOURCES}]")
+    n, h, w = depths.shape
+    dev = depths.device
+    nsteps = len(PCD_STEPS) if stages is None else int(stages)
+    if not 1 <= nsteps <= len(PCD_STEPS):
+        raise ValueError(f"stages={stages} out of range [1, {len(PCD_STEPS)}]")
+    cams = torch.from_numpy(pcd_cameras(K, E)).to(dev)
+    srcs = torch.from_numpy(pcd_sources(src_table, n, view)).to(dev)
+    need = int(np.ceil(np.float32(vthresh - 1.1)))
+    # step 1 (probability filter) in torch: mask = prob > 0.8; depth *= mask
+    masks = (probs > PCD_PROB_THRESHOLD).to(torch.uint8).contiguous()
+    depths = (_f32c(depths) * masks).contiguous()
+    ws, counts, m = pcd_steps(depths, masks, cams, srcs, need, 1, nsteps - 1) if nsteps > 1 else \
+        pcd_steps(depths, masks, cams, srcs, need, 1, 0)
+    out = {"depths": depths, "masks": masks.bool(), "counts": counts}
+    if stages is not None:
+        return out
+    xyz = torch.empty((m, 3), device=dev, dtype=torch.float32)
+    rgb = torch.empty((m, 3), device=dev, dtype=torch.uint8)
+    dirs = torch.empty((m, 3), device=dev, dtype=torch.float32)
+    if m:
+        images = images.contiguous()
+        _abi("mdf_pcd_compact", (depths.data_ptr(), masks.data_ptr(), images.data_ptr(), cams.data_ptr(), n, h, w,
+                                 view, ws.data_ptr(), xyz.data_ptr(), rgb.data_ptr(), dirs.data_ptr(), m, _stream(depths)),
+             tag=f"{w}x{h} n{n}", work={"bytes": 5.0 * n * h * w + 27.0 * m, "bound": "hbm"})
+    out.update(xyz=xyz, rgb=rgb, dirs=dirs)
+    return out

@@ -110,3 +110,38 @@ def seeded_state_dict(reference_sd, seed=1, prob_gain=6.0):
                 a = a * prob_gain
         out[key] = torch.from_numpy(np.asarray(a, dtype=np.float32)).reshape(shape)
     return out
+
+
+def pcd_scan(n, h, w, seed=0, nsrc=10):
+    """Synthetic scan for the point-cloud fusion (ops.pcd_fuse): n cameras on a 2-D grid looking at a slanted plane, depth maps
+    by exact ray-plane intersection plus 0.02 % noise and 3 % outliers, probabilities in [0.6, 1), random RGB images and a
+    pair list of the nsrc nearest cameras.  -> dict(depths [n,h,w] f32, probs [n,h,w] f32, images [n,h,w,3] u8, K [n,3,3] f32,
+    E [n,4,4] f32, srcs list of lists)."""
+    rng = np.random.RandomState(seed)
+    f = 1.2 * w
+    K = np.array([[f, 0, w / 2.0], [0, f, h / 2.0], [0, 0, 1]], dtype=np.float64)
+    side = int(np.ceil(np.sqrt(n)))
+    C = np.array([[(i % side) * 12.0, (i // side) * 12.0, 0.0] for i in range(n)]) - np.array([side * 6.0, side * 6.0, 0.0])
+    nrm, c0 = np.array([0.1, -0.05, -1.0]), -600.0               # plane n.X = c0 (z = 600 + 0.1 x - 0.05 y)
+    ys, xs = np.meshgrid(np.arange(h) + 0.5, np.arange(w) + 0.5, indexing="ij")
+    rays = np.linalg.inv(K) @ np.stack([xs.ravel(), ys.ravel(), np.ones(h * w)])
+    depths, Ks, Es = [], [], []
+    for v in range(n):
+        a = rng.uniform(-0.02, 0.02, 3)
+        Rx = np.array([[1, 0, 0], [0, np.cos(a[0]), -np.sin(a[0])], [0, np.sin(a[0]), np.cos(a[0])]])
+        Ry = np.array([[np.cos(a[1]), 0, np.sin(a[1])], [0, 1, 0], [-np.sin(a[1]), 0, np.cos(a[1])]])
+        R = Rx @ Ry
+        E = np.eye(4)
+        E[:3, :3] = R
+        E[:3, 3] = -R @ C[v]
+        t = (c0 - nrm @ C[v]) / (nrm @ (R.T @ rays))
+        d = t.reshape(h, w) * (1 + 2e-4 * rng.standard_normal((h, w)))
+        out = rng.rand(h, w) < 0.03
+        d[out] *= rng.uniform(0.8, 1.2, int(out.sum()))
+        depths.append(d.astype(np.float32))
+        Ks.append(K.astype(np.float32))
+        Es.append(E.astype(np.float32))
+    dist = np.linalg.norm(C[:, None] - C[None], axis=-1)
+    srcs = [[int(j) for j in np.argsort(dist[i], kind="stable") if j != i][:nsrc] for i in range(n)]
+    return {"depths": np.stack(depths), "probs": rng.uniform(0.6, 1.0, (n, h, w)).astype(np.float32),
+            "images": rng.randint(0, 256, (n, h, w, 3)).astype(np.uint8), "K": np.stack(Ks), "E": np.stack(Es), "srcs": srcs}

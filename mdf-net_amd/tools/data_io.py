@@ -88,18 +88,45 @@ def read_img(filename):
     return np.array(Image.open(filename), dtype=np.float32) / 255.0
 
 
-def write_ply(path, xyz, rgb):
-    """Vertices with float x,y,z (15 bytes each) + uchar red,green,blue; binary_little_endian 1.0 (what PlyData([el]).write produces)."""
+def write_ply(path, xyz, rgb, normals=None):
+    """Vertices with float x,y,z (15 bytes each) + uchar red,green,blue; binary_little_endian 1.0 (what PlyData([el]).write produces).
+    With normals [M,3], float nx,ny,nz follow z (27 bytes a vertex); read them back with read_ply_normals."""
     xyz = np.asarray(xyz, dtype="<f4").reshape(-1, 3)
     rgb = np.asarray(rgb, dtype=np.uint8).reshape(-1, 3)
-    rec = np.empty(len(xyz), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals is not None:
+        normals = np.asarray(normals, dtype="<f4").reshape(-1, 3)
+        if len(normals) != len(xyz):
+            raise ValueError(f"{len(normals)} normals for {len(xyz)} points")
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    rec = np.empty(len(xyz), dtype=fields + [("red", "u1"), ("green", "u1"), ("blue", "u1")])
     rec["x"], rec["y"], rec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    nprops = ""
+    if normals is not None:
+        rec["nx"], rec["ny"], rec["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
+        nprops = "property float nx\nproperty float ny\nproperty float nz\n"
     rec["red"], rec["green"], rec["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
     header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % len(rec))
+              "%sproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % (len(rec), nprops))
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
         rec.tofile(f)
+
+
+def read_ply_normals(path):
+    """The normals variant of write_ply -> (xyz [M,3] f32, rgb [M,3] u8, normals [M,3] f32)."""
+    with open(path, "rb") as f:
+        n = None
+        while True:
+            line = f.readline().decode("ascii").strip()
+            if line.startswith("element vertex"):
+                n = int(line.split()[-1])
+            if line == "end_header":
+                break
+        rec = np.fromfile(f, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
+                                    ("red", "u1"), ("green", "u1"), ("blue", "u1")], count=n)
+    return (np.stack([rec["x"], rec["y"], rec["z"]], 1), np.stack([rec["red"], rec["green"], rec["blue"]], 1),
+            np.stack([rec["nx"], rec["ny"], rec["nz"]], 1))
 
 
 def read_ply(path):
