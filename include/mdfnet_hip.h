@@ -284,6 +284,45 @@ int mdf_pcd_compact(const float* depths, const unsigned char* masks, const unsig
                     int w, int v, void* workspace, float* xyz, unsigned char* rgb_out, float* dirs, long long capacity,
                     void* stream);
 
+/* ---- DTU point-cloud evaluation (the MATLAB scorer: reducePts_haa.m, MaxDistCP.m, PointCompareMain.m), fp64 throughout --------
+ * Spatial index over n points pts [n][3] fp64: mdf_pts_index_workspace(n) bytes, 16-byte aligned, filled by mdf_pts_index_build (63-bit
+ * Morton keys over the points' bounding box, a stable radix sort, leaves of 32 sorted points under an implicit binary tree of
+ * AABBs).  The index holds a copy of the points; pts may be freed after the build.  Every call below that reads an index takes its
+ * n and its buffer size (index_bytes) and refuses a buffer smaller than mdf_pts_index_workspace(n).
+ * Distances: d^2 = ((dx*dx) + dy*dy) + dz*dz without contraction, d = sqrt(d^2), all correctly rounded.
+ *   mdf_pts_nn_dist    dist[i] = the nearest-neighbour distance of query i among the index's points if the query lies in the region
+ *                      and that distance is < cap, else cap (MaxDistCP(Qto = index, Qfrom = queries, BB, cap) below cap).  Queries:
+ *                      either `queries` [m][3] fp64 (results in query order) or `qindex`, another index over m points (its points
+ *                      are walked in key order and the results land at their input positions), not both.  bb: HOST [6] = BB(1,:),
+ *                      BB(2,:), or NULL for no region; the region is the union of MaxDistCP's cubes: on every axis a,
+ *                      fl(bb[a] + k*cap) <= q_a < fl(fl(bb[a] + k*cap) + cap) for some k in 0..floor((bb[3+a] - bb[a]) / cap).
+ *                      visits [m] int32 (or NULL): leaves visited per query.  n = 0 gives cap everywhere.
+ *   mdf_pts_reduce_*   reducePts_haa(pts, dst) for a given visiting order: rank [n] int32 (input indexing) is each point's position
+ *                      in the order (ties by input index).  A point is kept iff no kept point that precedes it lies within
+ *                      d <= dst: the sequential greedy result.  mdf_pts_reduce_count writes the number of (point, earlier
+ *                      neighbour) pairs to edges [1] int64 (device); then mdf_pts_reduce with resume = 0 places that CSR in
+ *                      csr [capacity] int32 (capacity >= edges) and runs up to max_rounds parallel rounds; resume = 1 runs
+ *                      max_rounds more from the same workspace.  keep [n] uint8 (0/1, input indexing) is written after every
+ *                      call; state [3] int32 (device, or NULL): rounds run, points still undecided (0 = done), 1 if the CSR did
+ *                      not fit (then no round runs).  workspace: mdf_pts_reduce_workspace(n) bytes, 16-byte aligned (22 B a point).
+ *   mdf_dtu_masks      DataInMask and StlAbovePlane of PointCompareMain.m: qdata [n][3], qstl [m][3] fp64; obs_mask uint8 0/1 of
+ *                      size s1 x s2 x s3 in MATLAB (column-major) order; bb HOST [6] (only bb[0..2] = BB(1,:) is read); plane
+ *                      HOST [4].  in_mask[i] = ObsMask(round((q - BB(1,:)) / res + 1)) inside [1, size], round() halving away
+ *                      from zero; above[j] = ((P1 x + P2 y) + P3 z) + P4 > 0.  in_mask / above [n] / [m] uint8.            */
+long long mdf_pts_index_workspace(long long n);
+int mdf_pts_index_build(const double* pts, long long n, void* index, long long index_bytes, void* stream);
+int mdf_pts_nn_dist(const void* index, long long n, long long index_bytes, const void* qindex, const double* queries, long long m,
+                    long long qindex_bytes, const double* bb, double cap, double* dist, int* visits, void* stream);
+long long mdf_pts_reduce_workspace(long long n);
+int mdf_pts_reduce_count(const void* index, long long n, long long index_bytes, const int* rank, double dst, void* workspace,
+                         long long ws_bytes, long long* edges, void* stream);
+int mdf_pts_reduce(const void* index, long long n, long long index_bytes, const int* rank, double dst, void* workspace,
+                   long long ws_bytes, int* csr, long long capacity, int resume, int max_rounds, unsigned char* keep, int* state,
+                   void* stream);
+int mdf_dtu_masks(const double* qdata, long long n, const unsigned char* obs_mask, int s1, int s2, int s3, const double* bb,
+                  double res, unsigned char* in_mask, const double* qstl, long long m, const double* plane, unsigned char* above,
+                  void* stream);
+
 /* =====================================================================================================
  * Training path (BASELINE config 3; train.py:36-45 -> loss.backward()).  The reference has no explicit backward:
  * autograd differentiates the op chains cited above.  Each entry below is the hand-written forward-in-train-mode or

@@ -64,6 +64,15 @@ SIGNATURES = {
     "mdf_pcd_fuse_workspace": (c_i64, [c_int, c_int, c_int, c_int]),
     "mdf_pcd_fuse_fwd": (c_int, [c_fp, c_fp, c_fp, c_fp] + [c_int] * 7 + [c_fp, c_fp, c_fp, c_fp]),
     "mdf_pcd_compact": (c_int, [c_fp, c_fp, c_fp, c_fp] + [c_int] * 4 + [c_fp, c_fp, c_fp, c_fp, c_i64, c_fp]),
+    "mdf_pts_index_workspace": (c_i64, [c_i64]),
+    "mdf_pts_index_build": (c_int, [c_fp, c_i64, c_fp, c_i64, c_fp]),
+    "mdf_pts_nn_dist": (c_int, [c_fp, c_i64, c_i64, c_fp, c_fp, c_i64, c_i64, ctypes.POINTER(ctypes.c_double), ctypes.c_double, c_fp,
+                                c_fp, c_fp]),
+    "mdf_pts_reduce_workspace": (c_i64, [c_i64]),
+    "mdf_pts_reduce_count": (c_int, [c_fp, c_i64, c_i64, c_fp, ctypes.c_double, c_fp, c_i64, c_fp, c_fp]),
+    "mdf_pts_reduce": (c_int, [c_fp, c_i64, c_i64, c_fp, ctypes.c_double, c_fp, c_i64, c_fp, c_i64, c_int, c_int, c_fp, c_fp, c_fp]),
+    "mdf_dtu_masks": (c_int, [c_fp, c_i64, c_fp, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_double, c_fp, c_fp,
+                              c_i64, ctypes.POINTER(ctypes.c_double), c_fp, c_fp]),
     "mdf_bn_stats_fwd": (c_int, [c_fp, c_i64, c_int, c_int, c_fp, c_fp]),
     "mdf_bn_finalize_fwd": (c_int, [c_fp, c_fp, c_fp, ctypes.c_float, ctypes.c_float, c_i64, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_fp]),
     "mdf_bn_relu_apply_fwd": (c_int, [c_fp, c_fp, c_fp, c_fp, c_i64, c_int, c_int, c_fp]),
@@ -144,3 +153,9 @@ def pcd_fuse(*args, **kwargs):
     """Point-cloud fusion of one scan (ops.pcd_fuse; the reference's tools/pcd/fusion.py:get_cloud)."""
     from .ops import pcd_fuse as _pcd_fuse
     return _pcd_fuse(*args, **kwargs)
+
+
+def dtu_eval_scan(*args, **kwargs):
+    """DTU point-cloud evaluation of one scan (ops.dtu_eval_scan; the reference's BaseEvalMain_web.m / PointCompareMain.m)."""
+    from .ops import dtu_eval_scan as _dtu_eval_scan
+    return _dtu_eval_scan(*args, **kwargs)

@@ -834,3 +834,210 @@ def pcd_fuse(depths, probs, images, K, E, src_table, view=10, vthresh=4, normals
              tag=f"{w}x{h} n{n}", work={"bytes": 5.0 * n * h * w + 27.0 * m, "bound": "hbm"})
     out.update(xyz=xyz, rgb=rgb, dirs=dirs)
     return out
+
+
+# --------------------------------------------------------------------------- DTU point-cloud evaluation (the MATLAB scorer)
+DTU_MAX_DIST_CP = 60.0         # PointCompareMain.m: MaxDist of MaxDistCP (cube size and distance cap)
+DTU_OUTLIER = 20.0             # BaseEvalMain_web.m / ComputeStat_web.m: MaxDist of the statistics
+DTU_MARGIN = 10                # the ObsMask{scan}_10.mat margin
+REDUCE_ROUNDS_PER_CALL = 32
+
+
+class PointIndex:
+    """A spatial index over n fp64 points on the GPU (mdf_pts_index_build): `buf` holds the points in Morton order, the
+    permutation back to the input order and the tree.  Build with point_index(pts)."""
+
+    def __init__(self, buf, n, device):
+        self.buf, self.n, self.device = buf, int(n), device
+
+    @property
+    def nbytes(self):
+        return int(self.buf.numel())
+
+
+def _pts64(pts, device=None):
+    """[n,3] array-like or tensor -> contiguous fp64 GPU tensor (host data is copied to `device`, default cuda:current)."""
+    if not torch.is_tensor(pts):
+        import numpy as np
+        pts = torch.from_numpy(np.ascontiguousarray(np.asarray(pts, dtype=np.float64)))
+    if not pts.is_cuda:
+        if device is None:
+            raise RuntimeError("mdfnet_hip ops run on an MI355X only (got a CPU tensor); there is no CPU fallback")
+        pts = pts.to(device)
+    pts = pts.to(torch.float64).reshape(-1, 3).contiguous() if pts.numel() else pts.new_zeros((0, 3), dtype=torch.float64)
+    return pts
+
+
+def point_index(pts):
+    """Spatial index over pts: GPU [n,3] (any float dtype; computed in fp64).  -> PointIndex.
+    Device memory: 52 B a point + 96 B a leaf slot (the tree over leaves of 32 points, rounded up to a power of two)."""
+    _need_gpu(pts)
+    pts = _pts64(pts)
+    n = pts.shape[0]
+    nbytes = int(lib().mdf_pts_index_workspace(n))
+    if nbytes <= 0 and n:
+        raise ValueError(f"point_index: {n} points are too many")
+    buf = torch.empty(max(nbytes, 16), device=pts.device, dtype=torch.uint8)
+    _abi("mdf_pts_index_build", (pts.data_ptr() if n else None, n, buf.data_ptr(), buf.numel(), _stream(buf)), tag=f"n{n}",
+         work={"points": float(n), "bound": "hbm"})
+    return PointIndex(buf, n, pts.device)
+
+
+def _host_doubles(vals, k):
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(vals, dtype=np.float64).reshape(-1))
+    if a.size != k:
+        raise ValueError(f"{k} values expected, got {a.size}")
+    return (ctypes.c_double * k)(*a.tolist())
+
+
+def nn_distance(index, queries, bb=None, cap=DTU_MAX_DIST_CP, return_visits=False):
+    """MaxDistCP(Qto = index's points, Qfrom = queries, BB, cap) of the DTU scorer (MaxDistCP.m): for every query the exact
+    nearest-neighbour distance if it is < cap and the query lies in BB's cubes of side cap, else cap.  queries: GPU [m,3] (fp64)
+    or a PointIndex (its points are walked in Morton order, so the lanes of a wave follow nearby paths); bb: [[x,y,z],[x,y,z]]
+    (BB(1,:), BB(2,:)) or None for no region.  -> dist [m] fp64 GPU (and the leaves visited per query, int32, with
+    return_visits)."""
+    if not isinstance(index, PointIndex):
+        raise TypeError("nn_distance: index must come from point_index()")
+    if isinstance(queries, PointIndex):
+        m, qidx, qpts, qbytes = queries.n, queries.buf.data_ptr(), None, queries.nbytes
+    else:
+        _need_gpu(queries)
+        q = _pts64(queries)
+        m, qidx, qpts, qbytes = q.shape[0], None, q.data_ptr(), 0
+    dev = index.device
+    dist = torch.empty(m, device=dev, dtype=torch.float64)
+    visits = torch.empty(m, device=dev, dtype=torch.int32) if return_visits else None
+    bbh = _host_doubles(bb, 6) if bb is not None else None
+    if m:
+        _abi("mdf_pts_nn_dist", (index.buf.data_ptr(), index.n, index.nbytes, qidx, qpts, m, qbytes, bbh, float(cap), dist.data_ptr(),
+                                 visits.data_ptr() if visits is not None else None, _stream(dist)),
+             tag=f"n{index.n} m{m}", work={"queries": float(m), "bound": "valu"})
+    return (dist, visits) if return_visits else dist
+
+
+def reduce_points(pts, dst, order, index=None, stats=None):
+    """reducePts_haa(pts, dst) for the visiting order `order` (a permutation of 0..n-1, first visited first): a point is kept iff
+    no kept point visited before it lies within distance <= dst -- the sequential greedy result, computed in parallel rounds.
+    pts: GPU [n,3]; order: int array-like or tensor; index: a PointIndex over pts to reuse.  -> (keep [n] bool GPU, rounds int).
+    With a dict `stats`, its "edges" (pairs of a point and an earlier neighbour) and "rounds" are filled in."""
+    import numpy as np
+    _need_gpu(pts)
+    pts = _pts64(pts)
+    n = pts.shape[0]
+    dev = pts.device
+    if not (float(dst) > 0 and np.isfinite(float(dst))):
+        raise ValueError(f"dst={dst} must be finite and > 0")
+    order = torch.as_tensor(np.asarray(order) if not torch.is_tensor(order) else order).to(dev, torch.int64).reshape(-1)
+    if order.numel() != n:
+        raise ValueError(f"order has {order.numel()} entries for {n} points")
+    rank = torch.empty(n, device=dev, dtype=torch.int32)
+    if n:
+        if bool(((order < 0) | (order >= n)).any()) or int(torch.bincount(order, minlength=n).max()) != 1:
+            raise ValueError("order must be a permutation of 0..n-1")
+        rank[order] = torch.arange(n, device=dev, dtype=torch.int32)
+    index = index if index is not None else point_index(pts)
+    if index.n != n:
+        raise ValueError(f"index over {index.n} points for {n} points")
+    ws = torch.empty(max(int(lib().mdf_pts_reduce_workspace(n)), 16), device=dev, dtype=torch.uint8)
+    edges = torch.zeros(1, device=dev, dtype=torch.int64)
+    args = (index.buf.data_ptr(), n, index.nbytes, rank.data_ptr() if n else None, ctypes.c_double(float(dst)), ws.data_ptr(), ws.numel())
+    _abi("mdf_pts_reduce_count", args + (edges.data_ptr(), _stream(ws)), tag=f"n{n}", work={"points": float(n), "bound": "valu"})
+    ne = int(edges.item())
+    csr = torch.empty(max(ne, 1), device=dev, dtype=torch.int32)
+    keep = torch.empty(max(n, 1), device=dev, dtype=torch.uint8)
+    state = torch.zeros(3, device=dev, dtype=torch.int32)
+    resume = 0
+    while True:
+        _abi("mdf_pts_reduce", args + (csr.data_ptr(), ne, resume, REDUCE_ROUNDS_PER_CALL, keep.data_ptr(), state.data_ptr(),
+                                       _stream(ws)), tag=f"n{n} e{ne}", work={"edges": float(ne), "bound": "latency"})
+        rounds, undecided, overflow = (int(x) for x in state.tolist())
+        if overflow:
+            raise RuntimeError(f"reduce_points: the neighbour lists did not fit ({ne} edges)")
+        if undecided == 0:
+            break
+        resume = 1
+    if stats is not None:
+        stats.update(edges=ne, rounds=rounds)
+    return keep[:n].bool(), rounds
+
+
+def dtu_masks(qdata, obs_mask, bb, res, qstl, plane):
+    """DataInMask and StlAbovePlane of PointCompareMain.m.  qdata [n,3], qstl [m,3]: GPU; obs_mask: the ObsMask array (MATLAB
+    dimension order [s1,s2,s3], as read_mat returns it), host or GPU; bb [2,3], res, plane [4]: host values.
+    -> (in_mask [n] bool, above [m] bool) on the GPU."""
+    import numpy as np
+    _need_gpu(qdata, qstl)
+    q, s = _pts64(qdata), _pts64(qstl)
+    dev = q.device
+    if torch.is_tensor(obs_mask):
+        dims = tuple(obs_mask.shape)
+        om = obs_mask.to(dev).permute(*reversed(range(obs_mask.dim()))).contiguous().reshape(-1).to(torch.uint8)
+    else:
+        a = np.asarray(obs_mask)
+        dims = a.shape
+        om = torch.from_numpy(np.ascontiguousarray(a.reshape(-1, order="F")).astype(np.uint8)).to(dev)
+    dims = tuple(dims) + (1,) * (3 - len(dims))
+    if len(dims) != 3:
+        raise ValueError(f"ObsMask must be 3-D, got shape {dims}")
+    n, m = q.shape[0], s.shape[0]
+    in_mask = torch.empty(max(n, 1), device=dev, dtype=torch.uint8)
+    above = torch.empty(max(m, 1), device=dev, dtype=torch.uint8)
+    om = om if om.numel() else torch.zeros(1, device=dev, dtype=torch.uint8)
+    _abi("mdf_dtu_masks", (q.data_ptr(), n, om.data_ptr(), int(dims[0]), int(dims[1]), int(dims[2]), _host_doubles(bb, 6),
+                           ctypes.c_double(float(res)), in_mask.data_ptr(), s.data_ptr(), m, _host_doubles(plane, 4), above.data_ptr(),
+                           _stream(q)), tag=f"n{n} m{m}", work={"points": float(n + m), "bound": "hbm"})
+    return in_mask[:n].bool(), above[:m].bool()
+
+
+def dtu_stats(d):
+    """ComputeStat_web.m on one filtered distance array (host): (count, mean, variance (n-1), median); NaN for an empty array
+    (MATLAB's mean / var / median of []), variance 0 for one value."""
+    import numpy as np
+    d = np.asarray(d, dtype=np.float64).reshape(-1)
+    if d.size == 0:
+        return 0, float("nan"), float("nan"), float("nan")
+    return int(d.size), float(np.mean(d)), float(np.var(d, ddof=1)) if d.size > 1 else 0.0, float(np.median(d))
+
+
+def dtu_scan_stats(ev, max_dist=DTU_OUTLIER):
+    """The per-scan statistics of BaseEvalMain_web.m / ComputeStat_web.m from a BaseEval dict (Ddata, DataInMask, Dstl,
+    StlAbovePlane): accuracy from Ddata[DataInMask & Ddata < max_dist], completeness from Dstl[StlAbovePlane & Dstl < max_dist]."""
+    import numpy as np
+    dd = np.asarray(ev["Ddata"], dtype=np.float64).reshape(-1)
+    ds = np.asarray(ev["Dstl"], dtype=np.float64).reshape(-1)
+    dd = dd[np.asarray(ev["DataInMask"], dtype=bool).reshape(-1)]
+    ds = ds[np.asarray(ev["StlAbovePlane"], dtype=bool).reshape(-1)]
+    nd, md, vd, medd = dtu_stats(dd[dd < max_dist])
+    ns, ms, vs, meds = dtu_stats(ds[ds < max_dist])
+    return {"nData": nd, "MeanData": md, "VarData": vd, "MedData": medd, "nStl": ns, "MeanStl": ms, "VarStl": vs, "MedStl": meds}
+
+
+def dtu_eval_scan(qdata, qstl, obs_mask, bb, res, plane, dst=0.2, seed=0, max_dist=DTU_OUTLIER, device=None):
+    """PointCompareMain.m + the statistics of one scan on the GPU.  qdata [N,3] (the method's points), qstl [M,3] (the STL
+    points), host arrays or GPU tensors; obs_mask, bb [2,3], res, plane [4] as stored in ObsMask{scan}_10.mat / Plane{scan}.mat.
+    Qdata is reduced to a minimum spacing of dst in the visiting order numpy.random.RandomState(seed).permutation(N) (MATLAB's
+    randperm stream cannot be reproduced), then Ddata = MaxDistCP(Qstl, Qdata, BB, 60), Dstl = MaxDistCP(Qdata, Qstl, BB, 60)
+    and the two masks.  -> dict with BaseEval's fields as host numpy (Qdata 3xN reduced, Ddata, Qstl 3xM, Dstl, DataInMask,
+    StlAbovePlane, GroundPlane, dst, Margin), the statistics of dtu_scan_stats, and Rounds / Edges of the reduction."""
+    import numpy as np
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    q = _pts64(qdata, dev)
+    s = _pts64(qstl, dev)
+    n = q.shape[0]
+    order = np.random.RandomState(seed).permutation(n)
+    stats = {}
+    keep, _ = reduce_points(q, dst, order, stats=stats)
+    qr = q[keep].contiguous()
+    bb = np.asarray(bb, dtype=np.float64).reshape(2, 3)
+    stl_index = point_index(s)
+    data_index = point_index(qr)
+    ddata = nn_distance(stl_index, data_index, bb=bb, cap=DTU_MAX_DIST_CP)
+    dstl = nn_distance(data_index, stl_index, bb=bb, cap=DTU_MAX_DIST_CP)
+    in_mask, above = dtu_masks(qr, obs_mask, bb, res, s, plane)
+    ev = {"Qdata": qr.cpu().numpy().T.copy(), "Ddata": ddata.cpu().numpy(), "Qstl": s.cpu().numpy().T.copy(), "Dstl": dstl.cpu().numpy(),
+          "DataInMask": in_mask.cpu().numpy(), "StlAbovePlane": above.cpu().numpy(),
+          "GroundPlane": np.asarray(plane, dtype=np.float64).reshape(4, 1), "dst": float(dst), "Margin": DTU_MARGIN,
+          "Rounds": stats["rounds"], "Edges": stats["edges"]}
+    ev.update(dtu_scan_stats(ev, max_dist))
+    return ev

@@ -145,3 +145,37 @@ def pcd_scan(n, h, w, seed=0, nsrc=10):
     srcs = [[int(j) for j in np.argsort(dist[i], kind="stable") if j != i][:nsrc] for i in range(n)]
     return {"depths": np.stack(depths), "probs": rng.uniform(0.6, 1.0, (n, h, w)).astype(np.float32),
             "images": rng.randint(0, 256, (n, h, w, 3)).astype(np.uint8), "K": np.stack(Ks), "E": np.stack(Es), "srcs": srcs}
+
+
+def dtu_eval_scene(n_stl, n_data, seed=0, views=4, outlier_frac=0.02, res=0.5, half=150.0):
+    """A seeded synthetic DTU evaluation scene (the inputs of the MATLAB scorer's PointCompareMain.m): an STL point set sampled on
+    the height field z = 20 sin(x/40) cos(y/50) over [-half, half]^2 (mm), a method's cloud of n_data points in which every
+    surface sample appears `views` times within 0.05 mm (overlapping fused views) with 0.3 mm of noise, plus outlier_frac
+    outliers up to 90 mm off the surface (past the 60 mm cap and outside BB), an ObsMask of resolution `res` (the voxels within
+    2 mm of the surface, for |x| < 0.8 half) and a ground plane z = -15.  -> dict(qstl [n_stl,3] f64, qdata [n_data,3] f32,
+    obs_mask bool [s1,s2,s3], bb [2,3], res, plane [4])."""
+    rng = np.random.RandomState(seed)
+
+    def surf(x, y):
+        return 20.0 * np.sin(x / 40.0) * np.cos(y / 50.0)
+
+    xy = rng.uniform(-half, half, (n_stl, 2))
+    qstl = np.stack([xy[:, 0], xy[:, 1], surf(xy[:, 0], xy[:, 1])], 1)
+    n_out = int(round(n_data * outlier_frac))
+    n_base = max(1, (n_data - n_out + views - 1) // views)
+    xy = rng.uniform(-half, half, (n_base, 2))
+    base = np.stack([xy[:, 0], xy[:, 1], surf(xy[:, 0], xy[:, 1]) + rng.normal(0.0, 0.3, n_base)], 1)
+    pts = np.repeat(base, views, 0)[:n_data - n_out] + rng.uniform(-0.05, 0.05, (n_data - n_out, 3))
+    out = rng.uniform(-half - 90.0, half + 90.0, (n_out, 3))
+    out[:, 2] = rng.uniform(-90.0, 90.0, n_out)
+    qdata = np.concatenate([pts, out])[rng.permutation(n_data)].astype(np.float32)
+    bb = np.array([[-half - 5.0, -half - 5.0, -30.0], [half + 5.0, half + 5.0, 30.0]])
+    dims = tuple(int(np.floor((bb[1, k] - bb[0, k]) / res)) + 1 for k in range(3))
+    gx = bb[0, 0] + res * np.arange(dims[0])
+    gy = bb[0, 1] + res * np.arange(dims[1])
+    gz = bb[0, 2] + res * np.arange(dims[2])
+    height = surf(gx[:, None], gy[None, :])                                        # [s1, s2]
+    obs = np.abs(gz[None, None, :] - height[:, :, None]) < 2.0
+    obs &= (np.abs(gx) < 0.8 * half)[:, None, None]
+    return {"qstl": qstl, "qdata": qdata, "obs_mask": obs, "bb": bb, "res": float(res),
+            "plane": np.array([0.0, 0.0, 1.0, 15.0])}

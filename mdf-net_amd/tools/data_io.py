@@ -150,3 +150,186 @@ def tocuda(data_batch, device, parallel=False):
         elif isinstance(v, dict):
             out[k] = {k2: v2.to(device) for k2, v2 in v.items()}
     return out
+
+
+# --------------------------------------------------------------------------- general PLY vertex reader (the DTU scorer's plyread)
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8",
+              "float64": "f8"}
+
+
+def _ply_header(f):
+    if f.readline().strip() != b"ply":
+        raise ValueError("not a PLY file")
+    fmt, elements = None, []
+    while True:
+        raw = f.readline()
+        if not raw:
+            raise ValueError("PLY header without end_header")
+        tok = raw.decode("ascii", "replace").split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append((tok[1], int(tok[2]), []))
+        elif tok[0] == "property":
+            if tok[1] == "list":
+                elements[-1][2].append((tok[4], None, (_PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]])))
+            else:
+                elements[-1][2].append((tok[2], _PLY_TYPES[tok[1]], None))
+        elif tok[0] == "end_header":
+            break
+    if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
+        raise ValueError(f"unknown PLY format {fmt}")
+    return fmt, elements
+
+
+def _ply_binary_rows(f, count, props, end):
+    """Rows of an element with list properties, one at a time -> {name: [values]} for the scalar properties."""
+    out = {name: [] for name, t, _ in props if t is not None}
+    for _ in range(count):
+        for name, t, lt in props:
+            if t is not None:
+                dt = np.dtype(end + t)
+                out[name].append(np.frombuffer(f.read(dt.itemsize), dtype=dt)[0])
+            else:
+                ct, it = np.dtype(end + lt[0]), np.dtype(end + lt[1])
+                k = int(np.frombuffer(f.read(ct.itemsize), dtype=ct)[0])
+                f.read(k * it.itemsize)
+    return out
+
+
+def read_ply_vertices(path):
+    """The x, y, z of a PLY file's vertex element as float64 [N,3], whatever the format (ascii, binary little / big endian), the
+    property types, the extra properties or the elements around it (what the DTU scorer's plyread returns as Mesh.vertex)."""
+    with open(path, "rb") as f:
+        fmt, elements = _ply_header(f)
+        if fmt == "ascii":
+            lines = iter(f.read().decode("ascii").split("\n"))
+            for name, count, props in elements:
+                rows = []
+                for _ in range(count):
+                    line = next(lines).split()
+                    while not line:
+                        line = next(lines).split()
+                    if name != "vertex":
+                        continue
+                    vals, k = {}, 0
+                    for pname, t, lt in props:
+                        if t is not None:
+                            vals[pname] = float(line[k])
+                            k += 1
+                        else:
+                            k += 1 + int(line[k])
+                    rows.append((vals["x"], vals["y"], vals["z"]))
+                if name == "vertex":
+                    return np.array(rows, dtype=np.float64).reshape(-1, 3)
+            raise ValueError(f"{path}: no vertex element")
+        end = "<" if fmt == "binary_little_endian" else ">"
+        for name, count, props in elements:
+            if all(t is not None for _, t, _ in props):
+                dt = np.dtype([(pname, end + t) for pname, t, _ in props])
+                if name == "vertex":
+                    rec = np.frombuffer(f.read(dt.itemsize * count), dtype=dt, count=count)
+                    return np.stack([rec["x"].astype(np.float64), rec["y"].astype(np.float64), rec["z"].astype(np.float64)], 1)
+                f.seek(dt.itemsize * count, 1)
+            else:
+                rows = _ply_binary_rows(f, count, props, end)
+                if name == "vertex":
+                    return np.stack([np.asarray(rows[a], dtype=np.float64) for a in ("x", "y", "z")], 1).reshape(-1, 3)
+        raise ValueError(f"{path}: no vertex element")
+
+
+# --------------------------------------------------------------------------- MAT-file level 5 (the DTU ObsMask / Plane files)
+_MI = {1: "i1", 2: "u1", 3: "i2", 4: "u2", 5: "i4", 6: "u4", 7: "f4", 9: "f8", 12: "i8", 13: "u8"}
+_MX = {6: "f8", 7: "f4", 8: "i1", 9: "u1", 10: "i2", 11: "u2", 12: "i4", 13: "u4", 14: "i8", 15: "u8"}
+_MI_MATRIX, _MI_COMPRESSED, _MI_INT8 = 14, 15, 1
+
+
+def _mat_elements(buf, end):
+    """(type, payload) of the data elements in buf (small elements: 2-byte type, 2-byte size, 4 bytes of data)."""
+    pos = 0
+    while pos + 8 <= len(buf):
+        t, nb = np.frombuffer(buf, dtype=end + "u4", count=2, offset=pos)
+        t, nb = int(t), int(nb)
+        if t >> 16:                                 # small data element
+            yield t & 0xFFFF, buf[pos + 4:pos + 4 + (t >> 16)]
+            pos += 8
+            continue
+        yield t, buf[pos + 8:pos + 8 + nb]
+        pos += 8 + (nb if t == _MI_COMPRESSED else (nb + 7) // 8 * 8)
+
+
+def _mat_matrix(payload, end):
+    sub = list(_mat_elements(payload, end))
+    flags = int(np.frombuffer(sub[0][1], dtype=end + "u4", count=1)[0])
+    cls, logical, cplx = flags & 0xFF, bool(flags & 0x200), bool(flags & 0x800)
+    dims = tuple(int(x) for x in np.frombuffer(sub[1][1], dtype=end + _MI[sub[1][0]]))
+    name = bytes(sub[2][1]).decode("ascii")
+    if cls not in _MX or cplx:
+        return name, None                            # struct / cell / char / sparse / complex: not needed here
+    t, data = sub[3]
+    arr = np.frombuffer(data, dtype=end + _MI[t]).astype(_MX[cls])
+    arr = arr.reshape(dims, order="F")
+    return name, (arr.astype(bool) if logical else arr)
+
+
+def read_mat(path):
+    """A MAT-file (level 5) -> {name: numpy array} for its numeric and logical arrays, in MATLAB's dimension order (column-major
+    data), compressed elements or not.  Other variables (structs, cells, strings, sparse, complex) are skipped."""
+    import zlib
+    with open(path, "rb") as f:
+        raw = f.read()
+    if len(raw) < 128:
+        raise ValueError(f"{path}: not a MAT-file")
+    end = {b"IM": "<", b"MI": ">"}.get(raw[126:128])
+    if end is None or raw[:6] == b"MATLAB" and b"7.3" in raw[:20]:
+        raise ValueError(f"{path}: not a level-5 MAT-file")
+    out = {}
+    for t, payload in _mat_elements(raw[128:], end):
+        if t == _MI_COMPRESSED:
+            inner = zlib.decompress(bytes(payload))
+            t, payload = next(_mat_elements(inner, end))
+        if t != _MI_MATRIX:
+            continue
+        name, arr = _mat_matrix(payload, end)
+        if arr is not None:
+            out[name] = arr
+    return out
+
+
+_MX_OF = {np.dtype("f8"): (6, 9), np.dtype("f4"): (7, 7), np.dtype("i1"): (8, 1), np.dtype("u1"): (9, 2), np.dtype("i2"): (10, 3),
+          np.dtype("u2"): (11, 4), np.dtype("i4"): (12, 5), np.dtype("u4"): (13, 6), np.dtype("i8"): (14, 12), np.dtype("u8"): (15, 13)}
+
+
+def _mat_el(t, payload):
+    pad = (-len(payload)) % 8
+    return np.array([t, len(payload)], dtype="<u4").tobytes() + payload + b"\0" * pad
+
+
+def write_mat(path, arrays):
+    """{name: array} -> an uncompressed little-endian MAT-file (level 5).  Numeric and bool arrays; a bool array is written as
+    a logical uint8 array, a scalar as 1x1, a vector as a row (1 x n), as MATLAB's save does."""
+    body = b""
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        logical = a.dtype == np.bool_
+        if logical:
+            a = a.astype(np.uint8)
+        a = a.astype(a.dtype.newbyteorder("<"))
+        if a.ndim == 0:
+            a = a.reshape(1, 1)
+        elif a.ndim == 1:
+            a = a.reshape(1, -1)
+        cls, mi = _MX_OF[np.dtype(a.dtype.str[1:])]
+        flags = cls | (0x200 if logical else 0)
+        sub = _mat_el(6, np.array([flags, 0], dtype="<u4").tobytes())
+        sub += _mat_el(5, np.array(a.shape, dtype="<i4").tobytes())
+        sub += _mat_el(_MI_INT8, name.encode("ascii"))
+        sub += _mat_el(mi, np.asfortranarray(a).tobytes(order="F"))
+        body += _mat_el(_MI_MATRIX, sub)
+    head = b"MATLAB 5.0 MAT-file, written by mdfnet tools/data_io.py".ljust(116, b" ") + b"\0" * 8 + \
+        np.array([0x0100], dtype="<u2").tobytes() + b"IM"
+    with open(path, "wb") as f:
+        f.write(head + body)
