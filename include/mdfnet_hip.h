@@ -85,6 +85,18 @@ int mdf_warp_aggregate_vec_fwd(const float* ref_fea, const float* const* src_fea
                                const float* w_params, float* cost, int cost_layout, int B, int C, int G,
                                int D, int h, int w, int n_src, void* stream);
 
+/* ---- a5d The same operator over PAIR-DIFFERENCE maps (eval).  With C/G = 2 the operator uses a feature
+ * pair only through softmax(a, b)[0] = 1 / (1 + exp(b - a)), and bilinear sampling is linear, so it can
+ * be fed d[g] = f[2g+1] - f[2g] (G channels) instead of f (C = 2G channels): half the tap bytes, half
+ * the blends.  Same sample positions and weights, same arithmetic from the similarity on; the result
+ * differs from mdf_warp_aggregate_vec_fwd by the rounding of the blend only.
+ *   ref_diff  [B,h,w,G] NHWC;  src_diffs  HOST array of n_src DEVICE pointers, each [B,h,w,G] NHWC
+ *   G in {8,16,32}; every other argument as mdf_warp_aggregate_vec_fwd                            */
+int mdf_warp_aggregate_pairdiff_fwd(const float* ref_diff, const float* const* src_diffs, int fea_layout,
+                                    const float* proj, const float* hypos, int hypos_per_pixel,
+                                    const float* w_params, float* cost, int cost_layout, int B, int G, int D,
+                                    int h, int w, int n_src, void* stream);
+
 /* ---- a5' homo_aggregate_by_variance (net/unit/homoaggregate.py:49-69) ------------------------
  * var = E[x^2] - E[x]^2 over {ref, softmax_C(warped src_v)}.  cost has C channels.               */
 int mdf_warp_aggregate_var_fwd(const float* ref_fea, const float* const* src_feas, int fea_layout,
@@ -165,7 +177,7 @@ int mdf_conv2d_pair_fwd(const float* x, const float* w1pack, const float* alpha1
  *      y[h] = [up2(res_ups[h]) +] W_h x + bias_h  for h < n_heads (2 or 3); x NHWC [B,H,W,Cin], y[h] NHWC [B,H,W,couts[h]],
  *      res_ups[h] [B,H/2,W/2,couts[h]] or NULL (bilinear x2, align_corners=False, added BEFORE nothing else: torch's order
  *      up + conv), biases[h] [couts[h]] or NULL, wpacks[h] = mdf_conv_pack_weights of head h (one tap).  The arrays are HOST arrays
- *      of device pointers.  Built: Cin 64 -> (64, 32, 16) and Cin 32 -> (32, 16); every output bit-identical to mdf_conv2d_fwd.  */
+ *      of device pointers.  Built: Cin 64 -> (64, 32, 16) and Cin 32 -> (32, 16), and their pair-difference forms Cin 64 -> (32, 16, 8), Cin 32 -> (16, 8); every output bit-identical to mdf_conv2d_fwd.  */
 int mdf_conv1x1_heads_fwd(const float* x, int n_heads, const float* const* wpacks, const float* const* biases,
                           const float* const* res_ups, float* const* ys, const int* couts, int B, int H, int W, int Cin,
                           void* stream);

@@ -48,7 +48,7 @@ __device__ __forceinline__ void pix_at(const PixBase& b, int delta, int Ho, int 
 
 template <int CIN, int COUT>
 __global__ __launch_bounds__(256) void conv1x1_kernel(const P1 p) {
-  constexpr int NCH = CIN / 16, NT = COUT / 16;
+  constexpr int NCH = CIN / 16, NT = (COUT + 15) / 16;     // COUT = 8: half a 16-row tile (the weight pack pads with zero rows); lanes q = 2, 3 idle in the epilogue
   constexpr int U = (8 / NCH) < 1 ? 1 : 8 / NCH;   // tiles per run: ~8 float4 loads in flight per lane
   const int lane = threadIdx.x & 63, q = lane >> 4, n16 = lane & 15;
   const int wave_g = blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = gridDim.x * 4;
@@ -67,8 +67,8 @@ __global__ __launch_bounds__(256) void conv1x1_kernel(const P1 p) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int c = nt * 16 + 4 * q + k;
-      al[nt][k] = p.alpha ? p.alpha[c] : 1.f;
-      be[nt][k] = p.beta ? p.beta[c] : 0.f;
+      al[nt][k] = (p.alpha && c < COUT) ? p.alpha[c] : 1.f;
+      be[nt][k] = (p.beta && c < COUT) ? p.beta[c] : 0.f;
     }
 
   for (int run = wave_g; run < p.n_runs; run += n_waves) {
@@ -104,6 +104,7 @@ __global__ __launch_bounds__(256) void conv1x1_kernel(const P1 p) {
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
         const int c0 = nt * 16 + 4 * q;
+        if (COUT % 16 != 0 && c0 >= COUT) continue;
         float o[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -161,7 +162,7 @@ struct P1M {
 template <int CIN, int C0, int C1, int C2, int U>      // U: tiles per run (the weights take NCH * NT * 4 registers)
 __global__ __launch_bounds__(256) void conv1x1_heads_kernel(const P1M p) {
   constexpr int NCH = CIN / 16;
-  constexpr int N0 = C0 / 16, N1 = C1 / 16, N2 = C2 / 16, NT = N0 + N1 + N2;
+  constexpr int N0 = (C0 + 15) / 16, N1 = (C1 + 15) / 16, N2 = (C2 + 15) / 16, NT = N0 + N1 + N2;     // an 8-channel head: half a tile, as conv1x1_kernel
   const int lane = threadIdx.x & 63, q = lane >> 4, n16 = lane & 15;
   const int wave_g = blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = gridDim.x * 4;
   auto head_of = [](int nt) { return nt < N0 ? 0 : (nt < N0 + N1 ? 1 : 2); };
@@ -176,7 +177,7 @@ __global__ __launch_bounds__(256) void conv1x1_heads_kernel(const P1M p) {
   float be[NT][4];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
-    const int h = head_of(nt), lt = nt - first_of(h), nth = cout_of(h) / 16;
+    const int h = head_of(nt), lt = nt - first_of(h), nth = (cout_of(h) + 15) / 16;
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) {
       if constexpr (WLDS) {
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(256) void conv1x1_heads_kernel(const P1M p) {
       }
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) be[nt][k] = p.beta[h] ? p.beta[h][lt * 16 + 4 * q + k] : 0.f;
+    for (int k = 0; k < 4; ++k) be[nt][k] = (p.beta[h] && lt * 16 + 4 * q + k < cout_of(h)) ? p.beta[h][lt * 16 + 4 * q + k] : 0.f;
   }
   if constexpr (WLDS) __syncthreads();
 
@@ -242,6 +243,7 @@ __global__ __launch_bounds__(256) void conv1x1_heads_kernel(const P1M p) {
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
         const int h = head_of(nt), co = cout_of(h), c0 = (nt - first_of(h)) * 16 + 4 * q;
+        if (co % 16 != 0 && c0 >= co) continue;
         float o[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) o[k] = acc[nt][k] * 1.0f + be[nt][k];          // (the single-head epilogue with alpha = 1)
@@ -306,6 +308,7 @@ int mdf_conv1x1_dispatch(const float* x, const float* wpack, const float* alpha,
   // (64 input channels stay on the LDS kernels: 2 tiles per run is all the registers allow, and that measured 1-2 us slower;
   //  non-temporal loads / stores measured slower too: 32->32 @296x400x5 50 -> 60 us inside a forward)
   C1_CASE(16, 16) C1_CASE(16, 32) C1_CASE(16, 64) C1_CASE(32, 16) C1_CASE(32, 32) C1_CASE(32, 64)
+  C1_CASE(16, 8)      // the pair-difference form of the 1/2-resolution head (net/unit/backbone.py:_composed_heads)
   return MDF_EUNSUPPORTED;
 }
 
@@ -331,5 +334,8 @@ extern "C" int mdf_conv1x1_heads_fwd(const float* x, int n_heads, const float* c
   // registers and one wave per SIMD; 32 -> 32/16 62.9 / 66.5 / 65.8 us at U = 1 / 2 / 4)
   if (Cin == 64 && n_heads == 3 && couts[0] == 64 && couts[1] == 32 && couts[2] == 16) return launch_heads<64, 64, 32, 16, 1>(p, st);
   if (Cin == 32 && n_heads == 2 && couts[0] == 32 && couts[1] == 16) return launch_heads<32, 32, 16, 0, 1>(p, st);
-  return mdf::fail(MDF_EUNSUPPORTED, "conv1x1 heads: Cin=%d with %d heads is not built (64 -> 64/32/16, 32 -> 32/16)", Cin, n_heads);
+  // the same heads emitting pair-difference maps (rows 2g+1 minus 2g of the composed matrices): half the output channels
+  if (Cin == 64 && n_heads == 3 && couts[0] == 32 && couts[1] == 16 && couts[2] == 8) return launch_heads<64, 32, 16, 8, 1>(p, st);
+  if (Cin == 32 && n_heads == 2 && couts[0] == 16 && couts[1] == 8) return launch_heads<32, 16, 8, 0, 1>(p, st);
+  return mdf::fail(MDF_EUNSUPPORTED, "conv1x1 heads: Cin=%d with %d heads is not built (64 -> 64/32/16, 32 -> 32/16, 64 -> 32/16/8, 32 -> 16/8)", Cin, n_heads);
 }

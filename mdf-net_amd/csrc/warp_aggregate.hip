@@ -382,6 +382,185 @@ int launch_vec8(Params& p, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// kVec over PAIR-DIFFERENCE maps.  With C/G = 2 the kernels above use a feature pair (a, b) = channels (2g, 2g+1) only through
+// softmax2_p0(a, b) = 1 / (1 + exp(b - a)), and the bilinear blend is linear: blend(b) - blend(a) = blend(b - a).  Fed the maps
+// d[g] = f[2g+1] - f[2g] ([B,h,w,G], written directly by the feature pyramid's composed heads: backbone.py:_composed_heads), a
+// tap is 4*G bytes instead of 8*G, a group costs one blend instead of two and the subtraction disappears.  Sample positions and
+// weights (phase A) are those of the kernels above with the texel stride G; from `sim` on the arithmetic and the operand order of
+// every sum are warp_vec8_kernel's / warp_kernel<16,kVec>'s, so with d computed exactly the only difference is the rounding of
+// the blend (one blend of a difference instead of the difference of two blends).
+// GPL = groups per lane (4 or 8): G / GPL lanes per pixel; at G = GPL a pixel is one lane and needs no cross-lane step.
+// FIXED: the tile's (pixel, view) pairs are one or two per thread, kept over the planes (warp_vec8_kernel's `few` / `two`, decided by
+// the launcher); else the generic tap-table loop.  Two instantiations instead of a branch: with both paths in one kernel the register
+// allocation is the generic path's (133 registers at GPL = 8, three waves per SIMD, instead of 96 and five).
+template <int G, int GPL, bool FIXED>
+__global__ __launch_bounds__(kThreads) void warp_pairdiff_kernel(const Params p) {
+  static_assert(GPL == 4 || GPL == 8, "groups per lane");
+  static_assert(G % GPL == 0, "a pixel is a whole number of lanes");
+  constexpr int LPP = G / GPL;         // lanes per pixel
+  constexpr int PPB = kThreads / LPP;  // pixels per block
+  constexpr int NQ = GPL / 4;          // 16-byte loads per tap and lane
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  TapEntry* tab = reinterpret_cast<TapEntry*>(smem);
+  const int hw = p.g.h * p.g.w;
+  const int b = blockIdx.y;
+  const PixTile<PPB> pt((int)mdf::xcd_remap(blockIdx.x, p.nblk_x), p.g.w);
+  const int tid = threadIdx.x;
+  const int pl = tid / LPP, sub = tid % LPP;
+  bool live;
+  const int pix = pt.pix(pl, p.g.w, p.g.h, live);
+
+  float rd[GPL], r1[GPL], cw[GPL];     // per group: r0 - r1, r1 of the reference softmax; conv weight
+#pragma unroll
+  for (int j = 0; j < NQ; ++j) {
+    const float4 rv = *reinterpret_cast<const float4*>(p.ref + ((size_t)b * hw + pix) * G + GPL * sub + 4 * j);
+    const float d4[4] = {rv.x, rv.y, rv.z, rv.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float p0 = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(d4[k] * kLog2e));   // softmax2_p0(a, b), d = b - a
+      const float p1 = 1.0f - p0;
+      rd[4 * j + k] = p0 - p1; r1[4 * j + k] = p1;
+      cw[4 * j + k] = p.wpar[GPL * sub + 4 * j + k];
+    }
+  }
+  const float alpha = p.wpar[G], beta = p.wpar[G + 1], w2 = p.wpar[G + 2], b2 = p.wpar[G + 3];
+  const size_t map_stride = (size_t)hw * G;
+  const unsigned lane_b = 4u * GPL * (unsigned)sub;   // byte offset of this lane's groups inside a texel
+
+  // tap table: as warp_vec8_kernel (a thread keeps up to two (pixel, view) pairs over the planes)
+  const int npair = PPB * p.n_src;
+  const bool few = (npair <= kThreads) && (kThreads % npair) == 0;
+  const bool two = (npair == 2 * kThreads);
+  const int pa_ngrp = few ? kThreads / npair : 1, pa_grp = few ? tid / npair : 0;
+  PixelRay ray[2];
+  int pa_pl[2], pa_v[2], pa_pix[2];
+  if constexpr (FIXED) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int pair = (few ? tid % npair : tid) + k * kThreads;
+      pa_pl[k] = pair % PPB; pa_v[k] = min(pair / PPB, p.n_src - 1);
+      bool pa_live;
+      pa_pix[k] = pt.pix(pa_pl[k], p.g.w, p.g.h, pa_live);
+      const int yy = pa_pix[k] / p.g.w, xx = pa_pix[k] - yy * p.g.w;
+      ray[k] = warp_ray(p.proj + ((size_t)pa_v[k] * p.B + b) * 12, (float)xx, (float)yy);
+    }
+  }
+
+  for (int d0 = 0; d0 < p.D; d0 += p.dchunk) {
+    const int nd = min(p.dchunk, p.D - d0);
+    if constexpr (FIXED) {
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        if (k == 1 && !two) break;
+        for (int ed = pa_grp; ed < nd; ed += pa_ngrp) {
+          const int d = d0 + ed;
+          const float dep = p.hypos_per_pixel ? p.hypos[((size_t)b * p.D + d) * hw + pa_pix[k]] : p.hypos[(size_t)b * p.D + d];
+          float ix, iy;
+          warp_position_ray(ray[k], dep, p.g, ix, iy);
+          TapEntry t;
+          make_taps(ix, iy, p.g, G, t);
+          tab[(ed * p.n_src + pa_v[k]) * PPB + pa_pl[k]] = t;
+        }
+      }
+    } else {
+      const int nent = nd * p.n_src * PPB;
+      for (int e = tid; e < nent; e += kThreads) {
+        const int epl = e % PPB;
+        const int ev = (e / PPB) % p.n_src;
+        const int ed = e / (PPB * p.n_src);
+        bool elive;
+        const int epix = pt.pix(epl, p.g.w, p.g.h, elive);
+        const int yy = epix / p.g.w, xx = epix - yy * p.g.w;
+        const float* m = p.proj + ((size_t)ev * p.B + b) * 12;
+        const int d = d0 + ed;
+        const float dep = p.hypos_per_pixel ? p.hypos[((size_t)b * p.D + d) * hw + epix] : p.hypos[(size_t)b * p.D + d];
+        float ix, iy;
+        warp_position(m, (float)xx, (float)yy, dep, p.g, ix, iy);
+        TapEntry t;
+        make_taps(ix, iy, p.g, G, t);
+        tab[e] = t;
+      }
+    }
+    __syncthreads();
+    for (int dd = 0; dd < nd; ++dd) {
+      float acc[GPL];
+#pragma unroll
+      for (int k = 0; k < GPL; ++k) acc[k] = 0.f;
+      float wsum = 0.f;
+      for (int v = 0; v < p.n_src; ++v) {
+        const TapEntry t = tab[(dd * p.n_src + v) * PPB + pl];
+        const char* sb = reinterpret_cast<const char*>(p.src[v] + (size_t)b * map_stride);
+        float sim[GPL];
+        float part = 0.f;
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {
+          const unsigned lb = lane_b + 16u * j;
+          const float4 nw = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[0] * 4u + lb));
+          const float4 ne = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[1] * 4u + lb));
+          const float4 sw = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[2] * 4u + lb));
+          const float4 se = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[3] * 4u + lb));
+          float dv[4];   // ATen tap order: nw*w + ne*w + sw*w + se*w, each step one fma
+          dv[0] = __fmaf_rn(se.x, t.wt[3], __fmaf_rn(sw.x, t.wt[2], __fmaf_rn(ne.x, t.wt[1], __fmul_rn(nw.x, t.wt[0]))));
+          dv[1] = __fmaf_rn(se.y, t.wt[3], __fmaf_rn(sw.y, t.wt[2], __fmaf_rn(ne.y, t.wt[1], __fmul_rn(nw.y, t.wt[0]))));
+          dv[2] = __fmaf_rn(se.z, t.wt[3], __fmaf_rn(sw.z, t.wt[2], __fmaf_rn(ne.z, t.wt[1], __fmul_rn(nw.z, t.wt[0]))));
+          dv[3] = __fmaf_rn(se.w, t.wt[3], __fmaf_rn(sw.w, t.wt[2], __fmaf_rn(ne.w, t.wt[1], __fmul_rn(nw.w, t.wt[0]))));
+          float q[2];    // the partial dot product of a 4-channel slice of the full-feature kernels (two groups)
+#pragma unroll
+          for (int h2 = 0; h2 < 2; ++h2) {
+            const int g0 = 4 * j + 2 * h2;
+            sim[g0] = __fmaf_rn(__builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(dv[2 * h2] * kLog2e)), rd[g0], r1[g0]);   // homoaggregate.py:38-39
+            sim[g0 + 1] = __fmaf_rn(__builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(dv[2 * h2 + 1] * kLog2e)), rd[g0 + 1], r1[g0 + 1]);
+            q[h2] = __fmaf_rn(cw[g0], sim[g0], cw[g0 + 1] * sim[g0 + 1]);
+          }
+          part = (j == 0) ? (q[0] + q[1]) : (part + (q[0] + q[1]));   // the first steps of those kernels' reduction trees, in the lane
+        }
+        float z = part;                                                          // Conv3d(G->1, 1x1x1)
+        if constexpr (LPP > 1) z = pixel_sum<LPP>(part);
+        const float u = __fmaf_rn(fmaxf(__fmaf_rn(z, alpha, beta), 0.0f), w2, b2);  // BN(eval) -> ReLU -> Conv3d(1->1)
+        const float wv = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-u * kLog2e));  // Sigmoid
+        wsum += wv;
+#pragma unroll
+        for (int k = 0; k < GPL; ++k) acc[k] += wv * sim[k];
+      }
+      if (!live) continue;
+      const size_t vox = ((size_t)b * p.D + d0 + dd) * hw + pix;
+      if (p.out_ndhwc) {
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {   // (non-temporal: see warp_vec8_kernel)
+          typedef float f4v __attribute__((ext_vector_type(4)));
+          f4v ov = {acc[4 * j] / wsum, acc[4 * j + 1] / wsum, acc[4 * j + 2] / wsum, acc[4 * j + 3] / wsum};   // homoaggregate.py:46
+          __builtin_nontemporal_store(ov, reinterpret_cast<f4v*>(p.out + vox * G + GPL * sub + 4 * j));
+        }
+      } else {
+        const size_t cs = (size_t)p.D * hw;
+        float* o = p.out + ((size_t)b * G * p.D + d0 + dd) * hw + pix;
+#pragma unroll
+        for (int k = 0; k < GPL; ++k) o[(size_t)(GPL * sub + k) * cs] = acc[k] / wsum;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+template <int G, int GPL>
+int launch_pairdiff(Params& p, hipStream_t st) {
+  constexpr int ppb = kThreads / (G / GPL);
+  p.nblk_x = PixTile<ppb>::blocks(p.g.w, p.g.h);
+  int dch = MDF_VEC8_TAB / (p.n_src * ppb);  // ~32 KiB of tap table per block, as warp_vec8_kernel
+  if (dch < 1) dch = 1;
+  if (dch > p.D) dch = p.D;
+  p.dchunk = dch;
+  const size_t lds = (size_t)dch * p.n_src * ppb * sizeof(TapEntry);
+  if (lds > 64 * 1024) return MDF_EUNSUPPORTED;
+  const int npair = ppb * p.n_src;
+  if ((npair <= kThreads && kThreads % npair == 0) || npair == 2 * kThreads)
+    hipLaunchKernelGGL((warp_pairdiff_kernel<G, GPL, true>), dim3(p.nblk_x, p.B), dim3(kThreads), lds, st, p);
+  else
+    hipLaunchKernelGGL((warp_pairdiff_kernel<G, GPL, false>), dim3(p.nblk_x, p.B), dim3(kThreads), lds, st, p);
+  return mdf::check_launch("warp_pairdiff_kernel");
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // kVec with LDS-staged source-feature tiles.  Per depth chunk the block finds, for every source view, the bounding box
 // of its taps in that view's feature map (min/max over the tap table), loads the boxes ONCE with coalesced row loads
 // (ww*C contiguous floats per window row in NHWC) into a pool of LDS windows, and takes the 4 bilinear taps of every
@@ -676,6 +855,46 @@ extern "C" int mdf_warp_aggregate_vec_fwd(const float* ref_fea, const float* con
     }
   }
   return launch<kVec>(p, C, (hipStream_t)stream);
+}
+
+extern "C" int mdf_warp_aggregate_pairdiff_fwd(const float* ref_diff, const float* const* src_diffs, int fea_layout,
+                                               const float* proj, const float* hypos, int hypos_per_pixel,
+                                               const float* w_params, float* cost, int cost_layout, int B, int G, int D,
+                                               int h, int w, int n_src, void* stream) {
+  MDF_REQUIRE(ref_diff && src_diffs && proj && hypos && w_params && cost, "null pointer argument");
+  MDF_REQUIRE(B > 0 && D > 0 && h > 1 && w > 1, "bad shape B=%d D=%d h=%d w=%d", B, D, h, w);
+  MDF_REQUIRE((long long)h * w * G < (1ll << 30), "feature map too large for 32-bit byte offsets");
+  MDF_REQUIRE(n_src >= 1 && n_src <= MDF_MAX_SRC_VIEWS, "n_src=%d out of range [1,%d]", n_src, MDF_MAX_SRC_VIEWS);
+  if (fea_layout != MDF_FEA_NHWC)
+    return mdf::fail(MDF_EUNSUPPORTED, "feature layout %d not supported (kernels gather NHWC taps)", fea_layout);
+  if (G != 8 && G != 16 && G != 32)
+    return mdf::fail(MDF_EUNSUPPORTED, "G=%d not supported (pair-difference maps are built for 8, 16, 32 groups)", G);
+  Params p{};
+  p.ref = ref_diff;
+  for (int v = 0; v < n_src; ++v) {
+    MDF_REQUIRE(src_diffs[v], "src_diffs[%d] is null", v);
+    p.src[v] = src_diffs[v];
+  }
+  p.proj = proj; p.hypos = hypos; p.wpar = w_params; p.out = cost;
+  p.g = make_geom(h, w);
+  p.B = B; p.D = D; p.n_src = n_src; p.hypos_per_pixel = hypos_per_pixel; p.out_ndhwc = (cost_layout == MDF_VOL_NDHWC);
+  hipStream_t st = (hipStream_t)stream;
+  // groups per lane: 4 on every stage.  Measured per launch at the cfg2 stage shapes, 5 views (scripts/bench_warp.py), 4 | 8 groups per
+  // lane: G 32 174 | 186 us, G 16 181 | 183 us, G 8 136 | 167 us (full features: 247, 274, 176 us).  With 8 the kernel needs 126
+  // registers (4 waves per SIMD, as the full-feature kernels) against 85 (5 waves), and at G = 8 a pixel is one lane with a 256-pixel
+  // tile: four (pixel, view) pairs per thread in phase A, one plane per table chunk.
+  int gpl = 4;
+  if (const char* e = getenv("MDF_PAIRDIFF_GPL")) { if (atoi(e) == 4 || atoi(e) == 8) gpl = atoi(e); }   // dev A/B (read per call)
+  if (gpl == 8) {
+    int rc = MDF_EUNSUPPORTED;
+    if (G == 32) rc = launch_pairdiff<32, 8>(p, st);
+    else if (G == 16) rc = launch_pairdiff<16, 8>(p, st);
+    else rc = launch_pairdiff<8, 8>(p, st);
+    if (rc != MDF_EUNSUPPORTED) return rc;     // (the tap table of a 256-pixel tile outgrows LDS beyond 8 source views)
+  }
+  if (G == 32) return launch_pairdiff<32, 4>(p, st);
+  if (G == 16) return launch_pairdiff<16, 4>(p, st);
+  return launch_pairdiff<8, 4>(p, st);
 }
 
 extern "C" int mdf_warp_aggregate_var_fwd(const float* ref_fea, const float* const* src_feas, int fea_layout,

@@ -33,6 +33,8 @@ SIGNATURES = {
     "mdf_warp_corner_indices": (c_int, [c_fp, c_fp, c_int, c_fp] + [c_int] * 4 + [c_fp]),
     "mdf_warp_aggregate_vec_fwd": (c_int, [c_fp, ctypes.POINTER(c_fp), c_int, c_fp, c_fp, c_int, c_fp, c_fp, c_int]
                                    + [c_int] * 7 + [c_fp]),
+    "mdf_warp_aggregate_pairdiff_fwd": (c_int, [c_fp, ctypes.POINTER(c_fp), c_int, c_fp, c_fp, c_int, c_fp, c_fp, c_int]
+                                        + [c_int] * 6 + [c_fp]),
     "mdf_warp_aggregate_var_fwd": (c_int, [c_fp, ctypes.POINTER(c_fp), c_int, c_fp, c_fp, c_int, c_fp, c_int]
                                    + [c_int] * 6 + [c_fp]),
     "mdf_conv3d_fwd": (c_int, [c_fp] * 6 + [c_int] * 9 + [c_fp]),

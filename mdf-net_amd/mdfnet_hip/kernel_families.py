@@ -27,7 +27,7 @@ KERNEL_FAMILY = {
     "wino3d_kernel": MFMA_CONV, "wino2d_kernel": MFMA_CONV,
     "pack_weights_kernel": CONTROL, "pack_batch_kernel": CONTROL,
     # warp_aggregate.hip
-    "warp_kernel": WARP, "warp_vec8_kernel": WARP, "warp_vec_win_kernel": WARP, "corner_index_kernel": WARP,
+    "warp_kernel": WARP, "warp_vec8_kernel": WARP, "warp_pairdiff_kernel": WARP, "warp_vec_win_kernel": WARP, "corner_index_kernel": WARP,
     # warp_aggregate_train.hip
     "warp_train_kernel": WARP_TRAIN, "warp_bwd_kernel": WARP_SCATTER,
     "agg_prepare_kernel": CONTROL, "agg_finalize_kernel": CONTROL, "agg_bwd_finalize_kernel": WARP_SCATTER,

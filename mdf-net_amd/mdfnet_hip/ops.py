@@ -210,6 +210,34 @@ def warp_aggregate_vec(features, proj, depth_hypos, w_params, ngroups, channels_
     return cost
 
 
+def warp_aggregate_pairdiff(diffs, proj, depth_hypos, w_params, channels_last=True):
+    """warp_aggregate_vec fed pair-difference maps: diffs = list of V [B,G,h,w] with d[:, g] = f[:, 2g+1] - f[:, 2g] (what the
+    built-in feature pyramid's difference heads emit).  Same arguments, result layout and sample positions; the cost differs from
+    warp_aggregate_vec(features) by the rounding of the bilinear blend only (one blend of a difference instead of the difference
+    of two blends)."""
+    _need_gpu(*diffs, proj, depth_hypos, w_params)
+    feas = [nhwc(f) for f in diffs]
+    b, g, h, w = feas[0].shape
+    if w_params.numel() != g + 4:
+        raise ValueError(f"w_params has {w_params.numel()} entries, expected G + 4 = {g + 4}: are these pair-difference maps?")
+    d = depth_hypos.shape[1]
+    hyp, pp = _hypos_arg(depth_hypos, h, w)
+    dev = feas[0].device
+    if channels_last:
+        mem = torch.empty((b, d, h, w, g), device=dev, dtype=torch.float32)
+        cost = mem.permute(0, 4, 1, 2, 3)
+    else:
+        mem = cost = torch.empty((b, g, d, h, w), device=dev, dtype=torch.float32)
+    srcs = feas[1:]
+    _abi("mdf_warp_aggregate_pairdiff_fwd", (feas[0].data_ptr(), _src_array(srcs), FEA_NHWC, _f32c(proj).data_ptr(),
+                                             hyp.data_ptr(), pp, _f32c(w_params).data_ptr(), mem.data_ptr(),
+                                             VOL_NDHWC if channels_last else VOL_NCDHW, b, g, d, h, w, len(srcs),
+                                             _stream(mem),), tag=f"G{g}D{d} {w}x{h} V{len(feas)}",
+         work={"bytes": 4.0 * b * (len(feas) * g * h * w + hyp.numel() / b + g * d * h * w),  # difference maps once + hypos once
+               "bound": "hbm"})                                                            # + cost once
+    return cost
+
+
 def warp_aggregate_var(features, proj, depth_hypos, channels_last=False):
     """Fused homo_aggregate_by_variance (homoaggregate.py:49-69) -> [B,C,D,h,w]."""
     _need_gpu(*features, proj, depth_hypos)

@@ -57,6 +57,15 @@ def _cut_features(feats, cuts):
     return out
 
 
+def _cached_form(cache, key):
+    """None: no pyramid under `key`; else whether the cached pyramid holds pair-difference maps.  (Looks without touching the
+    recency order of an LRU cache.)"""
+    if key not in cache:
+        return None
+    entry = dict.get(cache, key) if isinstance(cache, dict) else cache[key]
+    return bool(entry[2]) if len(entry) > 2 else False
+
+
 class CoreNet(torch.nn.Module):
     def __init__(self, Backbone, Depth_hypos, scale, Homoaggre, Regular, Regress, Refine):
         """Backbone: img -> 3 feature maps; Depth_hypos/Homoaggre/Regular: ModuleLists (one per stage);
@@ -81,22 +90,40 @@ class CoreNet(torch.nn.Module):
             with controlplane.active(plan):
                 return self._forward(origin_imgs, extrinsics, intrinsics, depth_range, feature_cache, view_keys)
 
-    def _pyramids(self, imgs, feature_cache, view_keys):
+    def _pair_diff_route(self, imgs):
+        """True when this forward runs on pair-difference pyramids: eval on a GPU, the built-in FPN_4Scales with the (8,16,32,64)
+        pyramid, and EVERY aggregation slot the built-in VectorAggregate with C/G = 2 -- the aggregation then reads a feature pair
+        (a, b) only through b - a, and nothing else reads the pyramid (the refinement net takes depth and range).  Any foreign
+        slot, variance aggregation or training: full features, as ever."""
+        from .unit import backbone as _bb
+        from .unit.homoaggregate import VectorAggregate
+        bb = self.Backbone
+        if not _bb._PAIR_DIFF or self.training or not imgs.is_cuda or type(bb) is not _bb.FPN_4Scales:
+            return False
+        chans = (bb.out4.out_channels, bb.out3.out_channels, bb.out2.out_channels)
+        if chans != (64, 32, 16) or (bb.out4.in_channels, bb.lat3.in_channels, bb.lat2.in_channels) != (64, 32, 16):
+            return False
+        slots = list(self.Homoaggre)
+        return len(slots) == 3 and all(type(a) is VectorAggregate and 2 * a.ngroups == c for a, c in zip(slots, chans))
+
+    def _pyramids(self, imgs, feature_cache, view_keys, pair_diff=False):
         nb, nv = imgs.shape[:2]
+        backbone = (lambda x: self.Backbone(x, pair_diff=True)) if pair_diff else self.Backbone
         if feature_cache is not None and view_keys is not None and nb == 1 and not self.training:
             if hasattr(feature_cache, "pin"):
                 feature_cache.pin(view_keys)                             # a bounded cache must keep this item's views
-            missing = [v for v in range(nv) if view_keys[v] not in feature_cache]
+            # (an entry carries the form of its pyramid: one of the other form -- the development switch flipped -- counts as missing)
+            missing = [v for v in range(nv) if _cached_form(feature_cache, view_keys[v]) is not pair_diff]
             if missing:
-                f = self.Backbone(imgs[0, missing])                      # only the images not seen yet, batched
+                f = backbone(imgs[0, missing])                           # only the images not seen yet, batched
                 ev = torch.cuda.Event()
                 ev.record()                                              # on the stream that produced them
                 for j, v in enumerate(missing):
-                    feature_cache[view_keys[v]] = (tuple(lv[j:j + 1] for lv in f), ev)
+                    feature_cache[view_keys[v]] = (tuple(lv[j:j + 1] for lv in f), ev, pair_diff)
             cur = torch.cuda.current_stream(imgs.device)
             out = []
             for v in range(nv):
-                pyr, ev = feature_cache[view_keys[v]]
+                pyr, ev = feature_cache[view_keys[v]][:2]
                 cur.wait_event(ev)                                       # another item in flight may have produced it
                 for t in pyr:
                     t.record_stream(cur)
@@ -106,9 +133,9 @@ class CoreNet(torch.nn.Module):
             return self.Backbone.forward_views(imgs)          # all views in one pass, BatchNorm statistics per view
         if getattr(self.Backbone, "batch_views", False) and not self.training:
             # eval BatchNorm is per-sample: one batched pass over the B*V images == V separate calls (core.py:42)
-            f = self.Backbone(imgs.reshape(nb * nv, *imgs.shape[2:]))
+            f = backbone(imgs.reshape(nb * nv, *imgs.shape[2:]))
             return [tuple(lv.reshape(nb, nv, *lv.shape[1:])[:, v] for lv in f) for v in range(nv)]
-        return [self.Backbone(v) for v in torch.unbind(imgs, 1)]
+        return [backbone(v) for v in torch.unbind(imgs, 1)]
 
     def _forward(self, origin_imgs, extrinsics, intrinsics, depth_range, feature_cache=None, view_keys=None):
         """imgs [B,V,3,H,W] (view 0 = reference), E [B,V,4,4], K [B,V,3,3], range [B,2]
@@ -125,7 +152,8 @@ class CoreNet(torch.nn.Module):
             from mdfnet_hip import train_ops
             with torch.no_grad():
                 train_ops.prepack(self)
-        pyramids = self._pyramids(origin_imgs.float(), feature_cache, view_keys)
+        pair_diff = self._pair_diff_route(origin_imgs)
+        pyramids = self._pyramids(origin_imgs.float(), feature_cache, view_keys, pair_diff)
         depth = hypos = prob = None
         depths = []
         # Training on the HIP kernels: every stage's aggregation + regulariser is issued on a stream of its own.  The forward pass
@@ -150,7 +178,8 @@ class CoreNet(torch.nn.Module):
             ref_proj, src_projs = self.scale(intrinsics, extrinsics, stage)
             with _on_stage_stream(side, stage, main if side else None, feats):
                 hypos = make_hypos(depth, depth_range, prob, hypos, upsample=True)
-                cost = aggregate(feats, ref_proj, src_projs, hypos)
+                # (pair_diff: the pyramids hold f[2g+1] - f[2g]; said explicitly, not inferred from the channel count)
+                cost = aggregate(feats, ref_proj, src_projs, hypos, pair_diff=True) if pair_diff else aggregate(feats, ref_proj, src_projs, hypos)
                 if ((not self.training or cost.is_cuda) and getattr(regular, "fused_regress", False)
                         and getattr(self.Depth_regress, "mdf_builtin", False)):
                     # both slots are the built-in ones: the soft-argmin (core.py:64) rides in the regulariser's softmax kernel

@@ -29,7 +29,15 @@ class VectorAggregate(nn.Module):
         sd = {k: v for k, v in self.depth_weight.state_dict(keep_vars=True).items()}
         return layers.cache_of(self).get(list(sd.values()), lambda: ops.fold_view_weight(sd, self.ngroups, prefix=""))
 
-    def forward(self, features, ref_proj, src_projs, depth_hypos):
+    def forward(self, features, ref_proj, src_projs, depth_hypos, pair_diff=False):
+        """pair_diff (eval on a GPU; set by CoreNet when it asked the backbone for them): `features` are the pair-difference maps
+        f[2g+1] - f[2g], [B,ngroups,h,w] each, instead of the [B,2*ngroups,h,w] features."""
+        if pair_diff:
+            if self.training or any(f.shape[1] != self.ngroups for f in features):
+                raise RuntimeError("pair-difference maps are an eval-mode input with ngroups channels")
+            with torch.no_grad():
+                proj = _projections(ref_proj, src_projs, features[0].device)
+                return ops.warp_aggregate_pairdiff(list(features), proj, depth_hypos, self._params())
         if layers.hip_train(self, *features, depth_hypos):
             # training on the GPU: two-pass batch-statistics BatchNorm3d(1), backward as an atomic scatter (train_ops.py)
             from mdfnet_hip import train_ops
