@@ -489,6 +489,23 @@ int mdf_aggregate_train_finalize(const double* red, const float* gamma, const fl
 int mdf_aggregate_train_bwd_finalize(const float* dhalf, const double* red, int n_src, long long n_half, float* dsrc,
                                      float* dpar, const float* dref_acc, float* dref, long long n_ref, void* stream);
 
+/* ---- backward of homo_aggregate_by_variance fused with the warp (homoaggregate.py:49-69; base.py:97: no gradient through the
+ *      sampling grid).  The operator has no parameters: its training forward is mdf_warp_aggregate_var_fwd with an
+ *      MDF_VOL_NDHWC cost volume, bit-identical to eval.  With N = n_src + 1, x_0 = ref, x_v = softmax_C(warp(src_v)),
+ *      m = sum_v x_v / N (recomputed from the features, never stored) and g = dcost:
+ *        dref          [B,h,w,C]  = sum_d (2/N) g (ref - m)                      (+= by the depth slices; zeroed by caller)
+ *        dsrc[v]       [B,h,w,C] += wt_k * x_v (gp - sum_c x_v gp), gp = (2/N) g (x_v - m), over the four bilinear taps of
+ *                      every sample (fp32 atomics; zeroed by caller; out-of-bounds taps receive nothing)
+ *      Features NHWC, C in {16,32,64}; dcost [B,D,h,w,C]; src_feas / dsrc HOST arrays of n_src DEVICE pointers.            */
+int mdf_warp_aggregate_var_bwd(const float* ref_fea, const float* const* src_feas, const float* proj, const float* hypos,
+                               int hypos_per_pixel, const float* dcost, float* dref, float* const* dsrc, int B, int C, int D,
+                               int h, int w, int n_src, void* stream);
+/*      Backward of mdf_homo_warp_fwd w.r.t. the source feature map (the transpose of the gather; the same kernel with the
+ *      soft-max stage compiled out):  dsrc [B,h,w,C] += wt_k * dvol over the four taps (zeroed by caller).
+ *      dvol [B,C,D,h,w] (MDF_VOL_NCDHW) or [B,D,h,w,C] (MDF_VOL_NDHWC); proj [B,12].                                       */
+int mdf_homo_warp_bwd(const float* dvol, int vol_layout, const float* proj, const float* hypos, int hypos_per_pixel,
+                      float* dsrc, int B, int C, int D, int h, int w, void* stream);
+
 /* ---- training loss (net/loss.py:10-27): sum over the output scales of smooth-L1 (beta 1, mean) over the pixels with
  *      gt > depth_min[b].  est, gt [B][per_batch] float; depth_min element b at floor_[b*floor_stride], float64 when
  *      floor_f64 (as the loader hands depth_range over) else float32.

@@ -149,11 +149,26 @@ prob_thresh = (0.0, 0.95, 1e-5)
 ngroups = (32, 16, 8)
 
 
-def build_model():
-    """A fresh CoreNet composed exactly like the reference's singleton."""
+AGGREGATES = ("vector", "variance")
+
+
+def build_model(aggregate="vector"):
+    """A fresh CoreNet.  aggregate="vector" (default): composed exactly like the reference's singleton.  aggregate="variance":
+    the classic MVSNet variance cost volume in the Homoaggre slots (homo_aggregate_by_variance, homoaggregate.py:49-69), whose
+    cost volume has the C = 2 G feature channels, so the regularisers' first layers are 64->16, 32->8, 16->8.  That model has no
+    `Homoaggre.*` parameters and differently shaped `Regular.{0,1,2}.conv01` first layers: reference checkpoints (and those of
+    the vector model) do not load into it."""
+    if aggregate not in AGGREGATES:
+        raise ValueError(f"aggregate={aggregate!r}: choose one of {AGGREGATES}")
     hypos = nn.ModuleList([HyposByFit(ndepths[i], curve_calss[i], prob_thresh[i]) for i in range(stages - 1)])
-    aggre = nn.ModuleList([VectorAggregate(ngroups[i]) for i in range(stages - 1)])
-    regular = nn.ModuleList([RegularNet_3Scales(ngroups[0])] + [RegularNet_4Scales(c) for c in ngroups[1:]])
+    if aggregate == "variance":
+        from net.unit.homoaggregate import homo_aggregate_by_variance
+        aggre = [homo_aggregate_by_variance] * (stages - 1)
+        in_chs = tuple(2 * g for g in ngroups)          # (64, 32, 16): the feature channels of the three stages
+    else:
+        aggre = nn.ModuleList([VectorAggregate(ngroups[i]) for i in range(stages - 1)])
+        in_chs = ngroups
+    regular = nn.ModuleList([RegularNet_3Scales(in_chs[0])] + [RegularNet_4Scales(c) for c in in_chs[1:]])
     return core.CoreNet(backbone.FPN_4Scales(chs), hypos, scale, aggre, regular,
                         [regress.depth_regression, regress.confidence_regress], refine.RefineNet2())
 

@@ -1500,6 +1500,8 @@ static int conv3d_entry(const float* x, const float* wpack, const float* alpha, 
   // stride 1 (every Cin x Cout the nets use)
   MDF_CONV_CASE(32, 16, kS1) MDF_CONV_CASE(16, 16, kS1) MDF_CONV_CASE(32, 32, kS1) MDF_CONV_CASE(64, 64, kS1)
   MDF_CONV_CASE(16, 8, kS1) MDF_CONV_CASE(8, 8, kS1) MDF_CONV_CASE(8, 16, kS1) MDF_CONV_CASE(16, 32, kS1)
+  // first layers of the regularisers behind the variance cost volume (C, not G, input channels) and their input gradients (training)
+  MDF_CONV_CASE(64, 16, kS1) MDF_CONV_CASE(32, 8, kS1) MDF_CONV_CASE(16, 64, kS1) MDF_CONV_CASE(8, 32, kS1)
   // stride 2
   MDF_CONV_CASE(16, 32, kS2) MDF_CONV_CASE(32, 64, kS2) MDF_CONV_CASE(8, 16, kS2)
   // transposed

@@ -102,6 +102,8 @@ def main():
     parser.add_argument("-p", "--pre_model", default=None, type=str, help="Pre training model")
     parser.add_argument("-d", "--dataset", default="dtu", type=str, choices=["dtu", "tanks"], help="Set dataset")
     parser.add_argument("-s", "--set", default="intermediate", type=str, choices=["intermediate", "advanced"])
+    parser.add_argument("--aggregate", default="vector", type=str, choices=list(config.AGGREGATES),
+                        help="cost-volume operator the checkpoint was trained with (train.py --aggregate)")
     args = parser.parse_args()
     logging.info(args)
     rank, world, local = shard.init()
@@ -114,7 +116,7 @@ def main():
         load_args, eval_args = config.LoadTanks(tanks_set=args.set), config.EvalTanks()
         from load.tankseval import LoadDataset
         dataset = LoadDataset(datasetpath=load_args.eval_root, scenelist=load_args.scenelist, nviews=eval_args.nviews)
-    model = config.model
+    model = config.model if args.aggregate == "vector" else config.build_model(aggregate=args.aggregate)
     if args.pre_model is not None:
         model.load_state_dict(torch.load(args.pre_model, map_location="cpu")["model"])
     model.to(eval_args.DEVICE)

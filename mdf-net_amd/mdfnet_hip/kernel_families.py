@@ -31,6 +31,8 @@ KERNEL_FAMILY = {
     # warp_aggregate_train.hip
     "warp_train_kernel": WARP_TRAIN, "warp_bwd_kernel": WARP_SCATTER,
     "agg_prepare_kernel": CONTROL, "agg_finalize_kernel": CONTROL, "agg_bwd_finalize_kernel": WARP_SCATTER,
+    # warp_variance_train.hip (backward of the variance aggregation and of the stand-alone warp)
+    "warp_var_bwd_kernel": WARP_SCATTER,
     # wgrad.hip / wgrad_lds.hip
     "wgrad_kernel": WGRAD, "wgrad_a1_kernel": WGRAD, "wgrad_a1_valu_kernel": WGRAD, "wgrad2d_kernel": WGRAD,
     "wgrad_lds_kernel": WGRAD, "wgrad_lds_batch_kernel": WGRAD, "slab_sum_kernel": WGRAD, "slab_sum_batch_kernel": WGRAD,

@@ -74,6 +74,18 @@ def hip_train(mod, *tensors):
     return training and len(ts) > 0 and all(t.is_cuda for t in ts)
 
 
+def hip_autograd(*tensors):
+    """Dispatch of the plain-FUNCTION slots that have training kernels of their own (homo_aggregate_by_variance, homo_warping):
+    True when all tensors are on a GPU and either the enclosing model is in training mode (`hip_train`) or the call stands alone
+    and a tensor requires grad with grad enabled.  Eval calls, CPU tensors and the rehearsal backend go where they always went."""
+    ts = [t for t in tensors if isinstance(t, torch.Tensor)]
+    if hip_train(None, *ts):
+        return True
+    if _TRAIN_STOCK and _REHEARSAL is not None:
+        return False
+    return len(ts) > 0 and all(t.is_cuda for t in ts) and torch.is_grad_enabled() and any(t.requires_grad for t in ts)
+
+
 def stock():
     """The rehearsal backend's slot functions (mdf-net_amd/rehearsal/stockops.py); raises unless it was selected."""
     if _REHEARSAL is None:

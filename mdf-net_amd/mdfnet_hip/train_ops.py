@@ -3,6 +3,8 @@
 
   AggregateTrainFn    Homoaggre[s] in training mode (net/unit/homoaggregate.py:25-46 with the batch-statistics
                       BatchNorm3d(1) of :16-20; gradient to the features only, base.py:97)
+  VarianceAggregateTrainFn / HomoWarpTrainFn   homo_aggregate_by_variance (homoaggregate.py:49-69) and homo_warping (base.py:85-126)
+                      with autograd: the eval forward kernels, one backward launch (csrc/warp_variance_train.hip)
   RegulariserTrainFn  Regular[s] + Depth_regress in training mode (net/unit/regular.py:47-69,114-133, regress.py:5-7):
                       every Conv3d/ConvTranspose3d + BatchNorm3d(batch statistics) + ReLU (+ skip) layer, the `prob`
                       conv, softmax over D and the soft-argmin, forward and backward
@@ -584,6 +586,89 @@ def aggregate_train(module, features, proj, hypos):
     if all(p is not None and p[0] is parents[0][0] and p[1] == i and p[2] == len(features) for i, p in enumerate(parents)):
         return AggregateTrainFn.apply(*args, len(features), parents[0][0])      # the views are the slices of one view-major tensor
     return AggregateTrainFn.apply(*args, 0, *features)
+
+
+# --------------------------------------------------------------------------- homo_aggregate_by_variance / homo_warping with autograd
+class VarianceAggregateTrainFn(torch.autograd.Function):
+    """homo_aggregate_by_variance (homoaggregate.py:49-69) with its backward on the HIP kernels.  The operator has no parameters
+    and no BatchNorm: the forward IS the eval kernel (mdf_warp_aggregate_var_fwd, NDHWC cost volume), bit-identical to eval;
+    the backward is one launch that recomputes the view mean per voxel (mdf_warp_aggregate_var_bwd)."""
+
+    @staticmethod
+    def forward(ctx, proj, hypos, nviews, *features):
+        """features: one [B,C,h,w] tensor per view -- or (nviews > 0) ONE view-major tensor [nviews*B,C,h,w] holding them all
+        (FPN_4Scales.forward_views), whose gradient is then returned as one tensor too (see AggregateTrainFn)."""
+        ctx.batched = nviews > 0
+        if ctx.batched:
+            allv = ops.nhwc(features[0].detach()).permute(0, 2, 3, 1).contiguous()              # [V*B,h,w,C] memory
+            bb = allv.shape[0] // nviews
+            feas = [allv[v * bb:(v + 1) * bb] for v in range(nviews)]
+        else:
+            feas = [ops.nhwc(f.detach()).permute(0, 2, 3, 1).contiguous() for f in features]  # [B,h,w,C] memory
+        b, h, w, c = feas[0].shape
+        d = hypos.shape[1]
+        hyp, pp = _hypos_arg(hypos.detach(), h, w)
+        nsrc = len(feas) - 1
+        projc = _f32c(proj)
+        cost = torch.empty((b, d, h, w, c), device=feas[0].device, dtype=torch.float32)
+        _abi("mdf_warp_aggregate_var_fwd", (feas[0].data_ptr(), _src_array(feas[1:]), ops.FEA_NHWC, projc.data_ptr(), hyp.data_ptr(), pp,
+                                            cost.data_ptr(), ops.VOL_NDHWC, b, c, d, h, w, nsrc, _stream(cost)),
+             tag=f"var train fwd C{c}D{d} {w}x{h} V{nsrc + 1}",
+             work={"bytes": 4.0 * b * ((nsrc + 1) * c * h * w + c * d * h * w), "bound": "hbm"})       # features once + cost once
+        ctx.feas, ctx.proj, ctx.hyp, ctx.pp, ctx.dims = feas, projc, hyp, pp, (b, c, d, h, w)
+        return cost.permute(0, 4, 1, 2, 3)          # [B,C,D,h,w] whose memory is NDHWC: what the regulariser reads without a layout pass
+
+    @staticmethod
+    def backward(ctx, dcost):
+        b, c, d, h, w = ctx.dims
+        feas, nsrc = ctx.feas, len(ctx.feas) - 1
+        dc = ops.to_ndhwc(dcost)
+        # one zero fill for every accumulator: d ref (the depth slices of a pixel add) | d src per view (the scatter's atomics)
+        dall = torch.zeros((nsrc + 1, b, h, w, c), device=feas[0].device, dtype=torch.float32)      # reference view first
+        _abi("mdf_warp_aggregate_var_bwd", (feas[0].data_ptr(), _src_array(feas[1:]), ctx.proj.data_ptr(), ctx.hyp.data_ptr(), ctx.pp,
+                                            dc.data_ptr(), dall[0].data_ptr(), _src_array([dall[v + 1] for v in range(nsrc)]),
+                                            b, c, d, h, w, nsrc, _stream(dall)),
+             tag=f"var train bwd C{c}D{d} {w}x{h} V{nsrc + 1}",
+             work={"bytes": 4.0 * b * (2 * (nsrc + 1) * c * h * w + c * d * h * w), "bound": "hbm"})   # features + their gradients once, dcost once
+        if ctx.batched:
+            dfeas = [dall.view((nsrc + 1) * b, h, w, c).permute(0, 3, 1, 2)]
+        else:
+            dfeas = [dall[v].permute(0, 3, 1, 2) for v in range(nsrc + 1)]
+        return (None, None, None) + tuple(dfeas)
+
+
+def variance_aggregate_train(features, proj, hypos):
+    parents = [getattr(f, "_mdf_parent", None) for f in features]
+    if all(p is not None and p[0] is parents[0][0] and p[1] == i and p[2] == len(features) for i, p in enumerate(parents)):
+        return VarianceAggregateTrainFn.apply(proj, hypos, len(features), parents[0][0])      # the views are the slices of one view-major tensor
+    return VarianceAggregateTrainFn.apply(proj, hypos, 0, *features)
+
+
+class HomoWarpTrainFn(torch.autograd.Function):
+    """homo_warping (base.py:85-126) with d src_fea on the HIP kernel (the scatter of mdf_warp_aggregate_var_bwd without its
+    soft-max stage).  The forward is ops.homo_warp, the eval call."""
+
+    @staticmethod
+    def forward(ctx, src_fea, proj12, hypos):
+        b, c, h, w = src_fea.shape
+        ctx.proj = _f32c(proj12)
+        ctx.hyp, ctx.pp = _hypos_arg(hypos.detach(), h, w)
+        ctx.dims = (b, c, hypos.shape[1], h, w)
+        return ops.homo_warp(src_fea.detach(), ctx.proj, hypos.detach())
+
+    @staticmethod
+    def backward(ctx, dvol):
+        b, c, d, h, w = ctx.dims
+        dv = _f32c(dvol)                                                   # [B,C,D,h,w], the layout the forward writes
+        dsrc = torch.zeros((b, h, w, c), device=dv.device, dtype=torch.float32)
+        _abi("mdf_homo_warp_bwd", (dv.data_ptr(), ops.VOL_NCDHW, ctx.proj.data_ptr(), ctx.hyp.data_ptr(), ctx.pp, dsrc.data_ptr(),
+                                   b, c, d, h, w, _stream(dsrc)),
+             tag=f"warp bwd C{c}D{d} {w}x{h}", work={"bytes": 4.0 * b * (c * h * w + c * d * h * w), "bound": "hbm"})
+        return dsrc.permute(0, 3, 1, 2), None, None
+
+
+def homo_warp_train(src_fea, proj12, hypos):
+    return HomoWarpTrainFn.apply(src_fea, proj12, hypos)
 
 
 # --------------------------------------------------------------------------- feature-pyramid trunk (2-D) in training mode

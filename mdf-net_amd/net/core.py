@@ -80,6 +80,8 @@ class CoreNet(torch.nn.Module):
         """Same call as the reference (net/core.py:30).  Optional, for whole-scan evaluation: a dict
         `feature_cache` and per-view hashable `view_keys` [V] (batch 1) -- feature pyramids are then computed once per
         image and reused while it serves as a source view of other items; results are identical."""
+        if self.training and origin_imgs.is_cuda and layers.hip_train(self, origin_imgs):
+            self._check_training_slots()
         with layers.model_mode(self.training):
             plan = None
             if origin_imgs.is_cuda:
@@ -105,6 +107,28 @@ class CoreNet(torch.nn.Module):
             return False
         slots = list(self.Homoaggre)
         return len(slots) == 3 and all(type(a) is VectorAggregate and 2 * a.ngroups == c for a, c in zip(slots, chans))
+
+    def _check_training_slots(self):
+        """Training on the GPU runs every stage slot on a hand-written training kernel; a slot that has none (a foreign module
+        or function) is refused HERE, when the training forward starts and before anything is launched, by name -- not halfway
+        through stage 0 by whichever kernel-less call comes first.  (The stock-op route for such compositions is the rehearsal
+        backend, `rehearsal.enable(on_gpu=True)`, under which this check is not reached.)"""
+        from .unit.homoaggregate import VectorAggregate, homo_aggregate_by_variance
+        from .unit.regular import RegularNet_3Scales, RegularNet_4Scales
+        bad = []
+        for s, a in enumerate(self.Homoaggre):
+            if type(a) is not VectorAggregate and a is not homo_aggregate_by_variance:
+                bad.append(f"Homoaggre[{s}] ({getattr(a, '__name__', type(a).__name__)})")
+        for s, r in enumerate(self.Regular):
+            if type(r) not in (RegularNet_3Scales, RegularNet_4Scales):
+                bad.append(f"Regular[{s}] ({type(r).__name__})")
+                if getattr(self.Depth_regress, "mdf_builtin", False):
+                    bad.append(f"Depth_regress behind the non-fused Regular[{s}] (stand-alone depth_regression)")
+        if bad:
+            raise RuntimeError("CoreNet.train() on a GPU: no hand-written training kernel for slot(s) " + ", ".join(bad) + "; built-in "
+                               "choices are VectorAggregate or homo_aggregate_by_variance, RegularNet_3Scales / RegularNet_4Scales with "
+                               "depth_regression.  The stock-op route is the rehearsal backend: `import rehearsal; "
+                               "rehearsal.enable(on_gpu=True)`")
 
     def _pyramids(self, imgs, feature_cache, view_keys, pair_diff=False):
         nb, nv = imgs.shape[:2]

@@ -50,7 +50,12 @@ class Res(nn.Module):
 
 def homo_warping(src_fea, src_proj, ref_proj, depth_hypos):
     """base.py:85-126.  src_fea [B,C,h,w]; projections [B,4,4]; hypos [B,D,1,1] | [B,D,h,w] -> [B,C,D,h,w]
-    (bit-identical to the reference's CPU result).  With autograd / on the CPU: the stock-op training path."""
+    (bit-identical to the reference's CPU result).  With autograd on a GPU: the same forward and the hand-written scatter as
+    d src_fea (train_ops.HomoWarpTrainFn; nothing flows to the sampling grid, base.py:97).  On the CPU: the rehearsal backend."""
+    if layers.hip_autograd(src_fea, depth_hypos):
+        from mdfnet_hip import train_ops
+        proj = ops.relative_projections(hostmirror.get(ref_proj), [hostmirror.get(src_proj)])[0]
+        return train_ops.homo_warp_train(src_fea, proj.to(src_fea.device, non_blocking=True), depth_hypos)
     if not layers.use_hip(None, src_fea, depth_hypos):
         return layers.stock().homo_warping(src_fea, src_proj, ref_proj, depth_hypos)
     proj = ops.relative_projections(hostmirror.get(ref_proj), [hostmirror.get(src_proj)])[0]

@@ -52,7 +52,13 @@ class VectorAggregate(nn.Module):
 
 
 def homo_aggregate_by_variance(features, ref_proj, src_projs, depth_hypos):
-    """homoaggregate.py:49-69: variance over {ref, softmax_C(warped src)} -> [B,C,D,h,w]."""
+    """homoaggregate.py:49-69: variance over {ref, softmax_C(warped src)} -> [B,C,D,h,w].  In training (an enclosing CoreNet in
+    training mode, or a feature that requires grad) on a GPU: the same forward kernel with an NDHWC cost volume and the
+    hand-written backward (train_ops.VarianceAggregateTrainFn)."""
+    if layers.hip_autograd(*features, depth_hypos):
+        from mdfnet_hip import train_ops
+        proj = _projections(ref_proj, src_projs, features[0].device)
+        return train_ops.variance_aggregate_train(list(features), proj, depth_hypos)
     if not layers.use_hip(None, *features, depth_hypos):
         return layers.stock().variance_aggregate(features, ref_proj, src_projs, depth_hypos)
     with torch.no_grad():

@@ -72,6 +72,8 @@ def main():
     parser.add_argument("-p", "--pre_model", default=None, type=str)
     parser.add_argument("-d", "--dataset", default="dtu", type=str, choices=["dtu", "blendedmvs"])
     parser.add_argument("-l", "--cmd_label", default="", type=str)
+    parser.add_argument("--aggregate", default="vector", type=str, choices=list(config.AGGREGATES),
+                        help="cost-volume operator of the Homoaggre slots: the reference's VectorAggregate, or the variance cost volume")
     args = parser.parse_args()
     rank, world, local = shard.init()
     if args.dataset == "dtu":
@@ -85,7 +87,7 @@ def main():
         from load.blendedtrain import LoadDataset
         dataset = LoadDataset(datasetpath=load_args.train_root, nviews=train_args.nviews, robust_train=train_args.robust)
     device = train_args.DEVICE
-    model = config.model
+    model = config.model if args.aggregate == "vector" else config.build_model(aggregate=args.aggregate)
     start_epoch = train_args.start_epoch
     if args.pre_model is not None:
         ckpt = torch.load(args.pre_model, map_location="cpu")
