@@ -335,6 +335,40 @@ int mdf_dtu_masks(const double* qdata, long long n, const unsigned char* obs_mas
                   double res, unsigned char* in_mask, const double* qstl, long long m, const double* plane, unsigned char* above,
                   void* stream);
 
+/* ---- Tanks and Temples F-score evaluation (crop volume, voxel-grid downsampling, point-to-point ICP), fp64 throughout ----------
+ * The spatial index, the distance formula and the rounding rules are those of the DTU section above.
+ *   mdf_pts_nn         mdf_pts_nn_dist's walk without a region, reporting which point was nearest: nearest[i] int32 = the INPUT
+ *                      index (the position in the pts the index was built from) of query i's nearest point if its distance is
+ *                      < cap, else -1; ties on d^2 go to the lowest input index.  dist [m] (or NULL): that distance, or cap;
+ *                      dist2 [m] (or NULL): d^2, or +inf; visits [m] (or NULL).  Queries as an array or as an index, as above.
+ *   mdf_pts_transform  out[i] = M p_i for a HOST 4x4 row-major matrix (rows 0..2 are read): x' = ((m00 x + m01 y) + m02 z) + m03,
+ *                      every operation rounded once.  out may be pts.
+ *   mdf_pts_crop       keep[i] uint8 = 1 iff axis_min <= p[axis] <= axis_max and (u, v) lies inside the polygon, HOST [k][2],
+ *                      3 <= k <= 64, where (u, v) = (y, z), (x, z), (x, y) for axis 0, 1, 2.  Even-odd rule: edge (i, j = i+1 mod k)
+ *                      counts iff (v_i < v && v_j >= v) || (v_j < v && v_i >= v) and u_i + ((v - v_i) / (v_j - v_i)) * (u_j - u_i) < u,
+ *                      each operation rounded once; inside = an odd count.  Points on an edge follow that formula.
+ *   mdf_pts_voxel_*    voxel-grid downsampling at cell size voxel: origin = (per-axis minimum of pts) - voxel/2, cell =
+ *                      floor((p - origin) / voxel) per axis, one output point per occupied cell = (0 + the cell's points summed in
+ *                      input order) / count, cells in ascending (x, y, z) cell order.  attrs [n][nattr] (nattr <= 6, or NULL with
+ *                      nattr = 0) are averaged the same way.  out_pts [n][3], out_attrs [n][nattr], out_count [n] int32 are sized
+ *                      for the worst case; m [1] int64 (device) receives the number of cells, or -1 when an axis needs more than
+ *                      2^21 cells (nothing is written then).  workspace: mdf_pts_voxel_workspace(n) bytes, 16-byte aligned.
+ *   mdf_pts_icp_sums   the sums of one point-to-point ICP step over the inliers (nearest[i] >= 0 and sqrt(dist2[i]) < threshold):
+ *                      src [n][3] the transformed source, tgt [nt][3] the target in input order.  out [17] (device): inlier count,
+ *                      sum of d^2, the source and target centroids, and H[a][b] = sum (s_a - cs_a)(t_b - ct_b) row-major.  Sums
+ *                      run over a fixed tree whose shape depends on n only.  workspace: mdf_pts_icp_workspace() bytes.      */
+int mdf_pts_nn(const void* index, long long n, long long index_bytes, const void* qindex, const double* queries, long long m,
+               long long qindex_bytes, double cap, double* dist, double* dist2, int* nearest, int* visits, void* stream);
+int mdf_pts_transform(double* out, const double* pts, long long n, const double* matrix, void* stream);
+int mdf_pts_crop(const double* pts, long long n, int axis, double axis_min, double axis_max, const double* polygon, int k,
+                 unsigned char* keep, void* stream);
+long long mdf_pts_voxel_workspace(long long n);
+int mdf_pts_voxel_downsample(const double* pts, const double* attrs, int nattr, long long n, double voxel, void* workspace,
+                             long long ws_bytes, double* out_pts, double* out_attrs, int* out_count, long long* m, void* stream);
+long long mdf_pts_icp_workspace(void);
+int mdf_pts_icp_sums(const double* src, long long n, const double* tgt, long long nt, const int* nearest, const double* dist2,
+                     double threshold, void* workspace, long long ws_bytes, double* out, void* stream);
+
 /* =====================================================================================================
  * Training path (BASELINE config 3; train.py:36-45 -> loss.backward()).  The reference has no explicit backward:
  * autograd differentiates the op chains cited above.  Each entry below is the hand-written forward-in-train-mode or

@@ -16,6 +16,8 @@
 //   masks      pts_dtu_masks_kernel: the ObsMask lookup (MATLAB round, 1-based column-major) and the ground-plane test.
 // Distances: d^2 = ((dx*dx) + dy*dy) + dz*dz, no contraction (the library builds with -ffp-contract=off; the pragma pins it here).
 // No float atomics; the only atomics are integer counters (per-block LDS histograms and the undecided count of a round).
+// The second half of the file ("registration and F-score") builds the Tanks and Temples protocol's pieces on the same index, sort
+// and distance helpers: nearest point with its index, rigid transform, crop volume, voxel-grid downsampling, ICP sums.
 #include <algorithm>
 #include <cmath>
 #include "common.h"
@@ -754,4 +756,504 @@ extern "C" int mdf_dtu_masks(const double* qdata, long long n, const unsigned ch
   if (m) for (int i = 0; i < 4; ++i) a.plane[i] = plane[i];
   hipLaunchKernelGGL(pts_dtu_masks_kernel, dim3(grid_of(k)), dim3(kBlock), 0, (hipStream_t)stream, a);
   return mdf::check_launch("pts_dtu_masks_kernel");
+}
+
+// ==================================================================================================== registration and F-score
+// The Tanks and Temples protocol's pieces (crop volume, voxel-grid downsampling, point-to-point ICP, F-score), on the index, sort and
+// distance helpers above:
+//   nn         pts_nn_idx_kernel: pts_nn_kernel's walk without a region, which also reports WHICH point was nearest (its input
+//              index; ties on d^2 go to the lowest input index, so a subtree at box distance == best is still walked).
+//   transform  pts_transform_kernel: x' = ((r00 x + r01 y) + r02 z) + t0, each operation rounded once.
+//   crop       pts_crop_kernel: the axis interval and an even-odd crossing count against the polygon.
+//   voxel      pts_bbox_*, pts_vox_key_kernel (3 x 21-bit cell keys, x major), the stable radix sort (a cell's points stay in input
+//              order), pts_vox_chunk_sum_kernel + pts_sort_scan_kernel + pts_vox_offsets_kernel (a three-pass exclusive scan of the
+//              segment heads over many blocks), pts_vox_mean_kernel (one lane per cell: sum in input order, divide).
+//   icp        pts_icp_moment_kernel<false> + pts_icp_final_kernel<false> (inlier count, sum of d^2, the two centroids),
+//              pts_icp_moment_kernel<true> + pts_icp_final_kernel<true> (the cross-covariance about them).  Every lane sums a fixed
+//              strided subset in order, every block folds its lanes with one fixed tree and one block folds the blocks the same
+//              way: the shape depends on n only, so the sums are run-independent.  No atomics.
+namespace {
+
+struct NnIdxArgs {
+  const double* pts;       // index points (key order)
+  const int* perm;         // key-order position -> input index
+  const double* nodes;
+  long long n, P;
+  const double* q;
+  const int* qperm;
+  long long m;
+  double cap, cap2;
+  double* dist;            // nullable
+  double* d2;              // nullable
+  int* nearest;
+  int* visits;             // nullable
+};
+
+__global__ __launch_bounds__(kBlock) void pts_nn_idx_kernel(const NnIdxArgs a) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= a.m) return;
+  const double qx = a.q[i * 3 + 0], qy = a.q[i * 3 + 1], qz = a.q[i * 3 + 2];
+  const long long out = a.qperm ? (long long)a.qperm[i] : i;
+  double best = INFINITY;
+  int bidx = 0x7fffffff;
+  int visits = 0;
+  if (a.n > 0) {
+    int stack[kStack];
+    double sd[kStack];
+    int sp = 0;
+    long long node = 1;
+    const double nd = box_dist2(a.nodes + 6, qx, qy, qz);
+    bool have = nd < a.cap2;
+    while (have) {
+      if (node >= a.P) {                         // leaf
+        ++visits;
+        const long long lo = (node - a.P) * kLeaf, hi = min(a.n, lo + kLeaf);
+        for (long long j = lo; j < hi; ++j) {
+          const double d2 = dist2(a.pts[j * 3 + 0], a.pts[j * 3 + 1], a.pts[j * 3 + 2], qx, qy, qz);
+          if (d2 <= best) {
+            const int pj = a.perm[j];
+            if (d2 < best || pj < bidx) { best = d2; bidx = pj; }
+          }
+        }
+      } else {
+        const long long c0 = 2 * node, c1 = c0 + 1;
+        const double d0 = box_dist2(a.nodes + c0 * 6, qx, qy, qz), d1 = box_dist2(a.nodes + c1 * 6, qx, qy, qz);
+        const long long nearc = d1 < d0 ? c1 : c0, farc = d1 < d0 ? c0 : c1;
+        const double dn = fmin(d0, d1), df = d1 < d0 ? d0 : d1;
+        if (df <= best && df < a.cap2 && sp < kStack) { stack[sp] = (int)farc; sd[sp] = df; ++sp; }
+        if (dn <= best && dn < a.cap2) { node = nearc; continue; }
+      }
+      have = false;
+      while (sp > 0) {
+        --sp;
+        if (sd[sp] <= best && sd[sp] < a.cap2) { node = stack[sp]; have = true; break; }
+      }
+    }
+  }
+  const bool found = best < a.cap2;
+  if (a.dist) a.dist[out] = found ? sqrt(best) : a.cap;
+  if (a.d2) a.d2[out] = found ? best : INFINITY;
+  a.nearest[out] = found ? bidx : -1;
+  if (a.visits) a.visits[out] = visits;
+}
+
+struct Affine { double r[12]; };     // rows of [R | t]
+
+__global__ __launch_bounds__(kBlock) void pts_transform_kernel(double* __restrict__ out, const double* __restrict__ pts, long long n,
+                                                               const Affine m) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const double x = pts[i * 3 + 0], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
+  for (int a = 0; a < 3; ++a)
+    out[i * 3 + a] = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(m.r[a * 4 + 0], x), __dmul_rn(m.r[a * 4 + 1], y)), __dmul_rn(m.r[a * 4 + 2], z)),
+                               m.r[a * 4 + 3]);
+}
+
+constexpr int kMaxPoly = 64;
+
+struct CropArgs {
+  const double* pts;
+  long long n;
+  int axis, iu, iv, k;
+  double amin, amax;
+  double poly[kMaxPoly][2];
+  unsigned char* keep;
+};
+
+// Edge (i, i+1) crosses the point's v when exactly one end lies below it (vi < y <= vj or vj < y <= vi); its crossing
+// u_i + ((y - v_i) / (v_j - v_i)) * (u_j - u_i) counts when it is < x.  Inside = an odd count.
+__global__ __launch_bounds__(kBlock) void pts_crop_kernel(const CropArgs a) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= a.n) return;
+  const double w = a.pts[i * 3 + a.axis], x = a.pts[i * 3 + a.iu], y = a.pts[i * 3 + a.iv];
+  int cnt = 0;
+  for (int e = 0; e < a.k; ++e) {
+    const int f = e + 1 < a.k ? e + 1 : 0;
+    const double ui = a.poly[e][0], vi = a.poly[e][1], uj = a.poly[f][0], vj = a.poly[f][1];
+    if ((vi < y && vj >= y) || (vj < y && vi >= y)) {
+      const double node = __dadd_rn(ui, __dmul_rn(__ddiv_rn(__dsub_rn(y, vi), __dsub_rn(vj, vi)), __dsub_rn(uj, ui)));
+      cnt += node < x ? 1 : 0;
+    }
+  }
+  a.keep[i] = (w >= a.amin && w <= a.amax && (cnt & 1)) ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- voxel grid
+constexpr int kVoxPer = 4, kVoxChunk = kBlock * kVoxPer;
+constexpr double kVoxMaxCell = 2097151.0;     // 2^21 - 1
+
+struct VoxelLayout {
+  long long n, ntiles, nchunks;
+  double* bbox_part;
+  double* bbox;
+  unsigned long long *key0, *key1;
+  int *val0, *val1;
+  int* hist;
+  long long* hoff;
+  int* chunk_sums;         // [nchunks] segment heads per chunk
+  long long* chunk_off;    // [nchunks]
+  int* seg_start;          // [n] first sorted position of segment g
+  long long* total;        // [1] segments
+  int* ctl;                // [4] ctl[0] = 1: more than 2^21 cells on an axis
+  long long bytes;
+};
+
+VoxelLayout voxel_layout(char* base, long long n) {
+  VoxelLayout L{};
+  L.n = n;
+  L.ntiles = (n + kTile - 1) / kTile;
+  L.nchunks = (n + kVoxChunk - 1) / kVoxChunk;
+  long long o = 0;
+  auto take = [&](long long bytes) { const long long at = o; o += align16(bytes); return base + at; };
+  L.bbox_part = reinterpret_cast<double*>(take(kBboxBlocks * 48));
+  L.bbox = reinterpret_cast<double*>(take(48));
+  L.key0 = reinterpret_cast<unsigned long long*>(take(n * 8));
+  L.key1 = reinterpret_cast<unsigned long long*>(take(n * 8));
+  L.val0 = reinterpret_cast<int*>(take(n * 4));
+  L.val1 = reinterpret_cast<int*>(take(n * 4));
+  L.hist = reinterpret_cast<int*>(take(kRadix * L.ntiles * 4));
+  L.hoff = reinterpret_cast<long long*>(take(kRadix * L.ntiles * 8));
+  L.chunk_sums = reinterpret_cast<int*>(take(L.nchunks * 4));
+  L.chunk_off = reinterpret_cast<long long*>(take(L.nchunks * 8));
+  L.seg_start = reinterpret_cast<int*>(take(n * 4));
+  L.total = reinterpret_cast<long long*>(take(8));
+  L.ctl = reinterpret_cast<int*>(take(16));
+  L.bytes = o;
+  return L;
+}
+
+__device__ __forceinline__ unsigned long long vox_cell(double x, double origin, double v) {
+  const double c = floor(__ddiv_rn(__dsub_rn(x, origin), v));
+  if (!(c > 0.0)) return 0;                         // also NaN
+  return c >= kVoxMaxCell ? 2097151ull : (unsigned long long)c;
+}
+
+__global__ __launch_bounds__(kBlock) void pts_vox_key_kernel(const double* __restrict__ pts, long long n, const double* __restrict__ bbox,
+                                                             double v, unsigned long long* __restrict__ keys, int* __restrict__ vals,
+                                                             int* __restrict__ ctl) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const double h = __dmul_rn(v, 0.5);
+  const double ox = __dsub_rn(bbox[0], h), oy = __dsub_rn(bbox[1], h), oz = __dsub_rn(bbox[2], h);
+  if (i == 0) {
+    bool fits = true;
+    for (int a = 0; a < 3; ++a) {
+      const double top = floor(__ddiv_rn(__dsub_rn(bbox[3 + a], __dsub_rn(bbox[a], h)), v));      // the greatest cell index
+      fits = fits && top <= kVoxMaxCell;              // false for NaN too
+    }
+    ctl[0] = fits ? 0 : 1;
+  }
+  const unsigned long long cx = vox_cell(pts[i * 3 + 0], ox, v), cy = vox_cell(pts[i * 3 + 1], oy, v), cz = vox_cell(pts[i * 3 + 2], oz, v);
+  keys[i] = (cx << 42) | (cy << 21) | cz;
+  vals[i] = (int)i;
+}
+
+__device__ __forceinline__ int vox_head(const unsigned long long* __restrict__ keys, long long s, long long n) {
+  if (s >= n) return 0;
+  return (s == 0 || keys[s] != keys[s - 1]) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(kBlock) void pts_vox_chunk_sum_kernel(const unsigned long long* __restrict__ keys, long long n,
+                                                                   int* __restrict__ sums) {
+  __shared__ int part[kBlock];
+  const long long base = (long long)blockIdx.x * kVoxChunk + threadIdx.x * kVoxPer;
+  int t = 0;
+  for (int k = 0; k < kVoxPer; ++k) t += vox_head(keys, base + k, n);
+  part[threadIdx.x] = t;
+  __syncthreads();
+  for (int off = kBlock / 2; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) sums[blockIdx.x] = part[0];
+}
+
+__global__ __launch_bounds__(kBlock) void pts_vox_offsets_kernel(const unsigned long long* __restrict__ keys, long long n,
+                                                                 const long long* __restrict__ chunk_off, int* __restrict__ seg_start) {
+  __shared__ int part[kBlock];
+  const long long base = (long long)blockIdx.x * kVoxChunk + threadIdx.x * kVoxPer;
+  int c[kVoxPer];
+  int t = 0;
+  for (int k = 0; k < kVoxPer; ++k) {
+    c[k] = vox_head(keys, base + k, n);
+    t += c[k];
+  }
+  part[threadIdx.x] = t;
+  __syncthreads();
+  for (int off = 1; off < kBlock; off <<= 1) {           // Hillis-Steele inclusive scan of the thread sums
+    const int add = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0;
+    __syncthreads();
+    part[threadIdx.x] += add;
+    __syncthreads();
+  }
+  long long run = chunk_off[blockIdx.x] + (part[threadIdx.x] - t);
+  for (int k = 0; k < kVoxPer; ++k) {
+    if (c[k]) seg_start[run] = (int)(base + k);          // run < heads in total <= n
+    run += c[k];
+  }
+}
+
+struct VoxMeanArgs {
+  const double* pts;
+  const double* attrs;     // [n][nattr] or null
+  int nattr;
+  long long n;
+  const int* order;        // sorted position -> input index
+  const int* seg_start;
+  const long long* total;
+  const int* ctl;
+  double* out_pts;
+  double* out_attrs;
+  int* out_count;
+  long long* m;
+};
+
+__global__ __launch_bounds__(kBlock) void pts_vox_mean_kernel(const VoxMeanArgs a) {
+  const long long g = (long long)blockIdx.x * kBlock + threadIdx.x;
+  const long long m = *a.total;
+  const bool refused = a.ctl[0] != 0;
+  if (g == 0) *a.m = refused ? -1 : m;
+  if (refused || g >= m) return;
+  const long long lo = a.seg_start[g], hi = g + 1 < m ? (long long)a.seg_start[g + 1] : a.n;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  double t[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (long long s = lo; s < hi; ++s) {
+    const long long i = a.order[s];
+    s0 = __dadd_rn(s0, a.pts[i * 3 + 0]);
+    s1 = __dadd_rn(s1, a.pts[i * 3 + 1]);
+    s2 = __dadd_rn(s2, a.pts[i * 3 + 2]);
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+      if (k < a.nattr) t[k] = __dadd_rn(t[k], a.attrs[i * a.nattr + k]);
+  }
+  const double cnt = (double)(hi - lo);
+  a.out_pts[g * 3 + 0] = __ddiv_rn(s0, cnt);
+  a.out_pts[g * 3 + 1] = __ddiv_rn(s1, cnt);
+  a.out_pts[g * 3 + 2] = __ddiv_rn(s2, cnt);
+#pragma unroll
+  for (int k = 0; k < 6; ++k)
+    if (k < a.nattr) a.out_attrs[g * a.nattr + k] = __ddiv_rn(t[k], cnt);
+  a.out_count[g] = (int)(hi - lo);
+}
+
+// ---------------------------------------------------------------------------------------------------- ICP sums
+constexpr int kIcpBlocks = 1024;
+constexpr int kIcpVals = 9;
+
+struct IcpArgs {
+  const double* src;       // [n][3] transformed source
+  const double* tgt;       // [nt][3] target, input order
+  const int* nearest;      // [n] target index or -1
+  const double* d2;        // [n]
+  long long n, nt;
+  double lim2;             // d < threshold <=> d2 < lim2
+  double* part;            // [kIcpBlocks][kIcpVals]
+  double* out;             // [17]: count, sum d2, source centroid, target centroid, H row-major
+};
+
+__device__ __forceinline__ void icp_block_fold(double (&v)[kIcpVals], double (*red)[kBlock]) {
+  for (int k = 0; k < kIcpVals; ++k) red[k][threadIdx.x] = v[k];
+  __syncthreads();
+  for (int s = kBlock / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s)
+      for (int k = 0; k < kIcpVals; ++k) red[k][threadIdx.x] = __dadd_rn(red[k][threadIdx.x], red[k][threadIdx.x + s]);
+    __syncthreads();
+  }
+}
+
+// kCov = false: v = (count, sum d2, sum s, sum t, 0); kCov = true: v = sum (s - cs)(t - ct)^T with the centroids of out[2..8).
+template <bool kCov>
+__global__ __launch_bounds__(kBlock) void pts_icp_moment_kernel(const IcpArgs a) {
+  __shared__ double red[kIcpVals][kBlock];
+  double v[kIcpVals] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double c[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (kCov)
+    for (int k = 0; k < 6; ++k) c[k] = a.out[2 + k];
+  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < a.n; i += (long long)gridDim.x * kBlock) {
+    const int j = a.nearest[i];
+    const double d2 = a.d2[i];
+    if (j < 0 || (long long)j >= a.nt || !(d2 < a.lim2)) continue;
+    const double sx = a.src[i * 3 + 0], sy = a.src[i * 3 + 1], sz = a.src[i * 3 + 2];
+    const double tx = a.tgt[(long long)j * 3 + 0], ty = a.tgt[(long long)j * 3 + 1], tz = a.tgt[(long long)j * 3 + 2];
+    if (!kCov) {
+      v[0] = __dadd_rn(v[0], 1.0);
+      v[1] = __dadd_rn(v[1], d2);
+      v[2] = __dadd_rn(v[2], sx); v[3] = __dadd_rn(v[3], sy); v[4] = __dadd_rn(v[4], sz);
+      v[5] = __dadd_rn(v[5], tx); v[6] = __dadd_rn(v[6], ty); v[7] = __dadd_rn(v[7], tz);
+    } else {
+      const double p[3] = {__dsub_rn(sx, c[0]), __dsub_rn(sy, c[1]), __dsub_rn(sz, c[2])};
+      const double q[3] = {__dsub_rn(tx, c[3]), __dsub_rn(ty, c[4]), __dsub_rn(tz, c[5])};
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int s = 0; s < 3; ++s) v[r * 3 + s] = __dadd_rn(v[r * 3 + s], __dmul_rn(p[r], q[s]));
+    }
+  }
+  icp_block_fold(v, red);
+  if (threadIdx.x < kIcpVals) a.part[(long long)blockIdx.x * kIcpVals + threadIdx.x] = red[threadIdx.x][0];
+}
+
+template <bool kCov>
+__global__ __launch_bounds__(kBlock) void pts_icp_final_kernel(const double* __restrict__ part, int nparts, double* __restrict__ out) {
+  __shared__ double red[kIcpVals][kBlock];
+  double v[kIcpVals] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int b = threadIdx.x; b < nparts; b += kBlock)
+    for (int k = 0; k < kIcpVals; ++k) v[k] = __dadd_rn(v[k], part[(long long)b * kIcpVals + k]);
+  icp_block_fold(v, red);
+  if (threadIdx.x == 0) {
+    if (!kCov) {
+      const double cnt = red[0][0];
+      out[0] = cnt;
+      out[1] = red[1][0];
+      for (int k = 0; k < 6; ++k) out[2 + k] = cnt > 0.0 ? __ddiv_rn(red[2 + k][0], cnt) : 0.0;
+    } else {
+      for (int k = 0; k < 9; ++k) out[8 + k] = red[k][0];
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int mdf_pts_nn(const void* index, long long n, long long index_bytes, const void* qindex, const double* queries, long long m,
+                          long long qindex_bytes, double cap, double* dist, double* dist2_out, int* nearest, int* visits, void* stream) {
+  if (int rc = check_index_args(index, n, index_bytes)) return rc;
+  MDF_REQUIRE(nearest || m == 0, "null pointer argument: nearest");
+  MDF_REQUIRE((qindex == nullptr) != (queries == nullptr) || m == 0, "exactly one of qindex and queries must be given");
+  MDF_REQUIRE(std::isfinite(cap) && cap > 0, "cap=%g must be finite and > 0", cap);
+  if (qindex) {
+    if (int rc = check_index_args(qindex, m, qindex_bytes)) return rc;
+  } else {
+    MDF_REQUIRE(m >= 0 && m < (1ll << 31), "m=%lld queries out of range", m);
+  }
+  if (m == 0) return MDF_OK;
+  const IndexLayout L = index_layout(static_cast<char*>(const_cast<void*>(index)), n);
+  NnIdxArgs a{};
+  a.pts = L.pts; a.perm = L.perm; a.nodes = L.nodes; a.n = n; a.P = L.P; a.m = m;
+  if (qindex) {
+    const IndexLayout Q = index_layout(static_cast<char*>(const_cast<void*>(qindex)), m);
+    a.q = Q.pts;
+    a.qperm = Q.perm;
+  } else {
+    a.q = queries;
+    a.qperm = nullptr;
+  }
+  a.cap = cap;
+  a.cap2 = sqrt_ge_bound(cap);
+  a.dist = dist; a.d2 = dist2_out; a.nearest = nearest; a.visits = visits;
+  hipLaunchKernelGGL(pts_nn_idx_kernel, dim3(grid_of(m)), dim3(kBlock), 0, (hipStream_t)stream, a);
+  return mdf::check_launch("pts_nn_idx_kernel");
+}
+
+extern "C" int mdf_pts_transform(double* out, const double* pts, long long n, const double* matrix, void* stream) {
+  MDF_REQUIRE(n >= 0 && n < (1ll << 40), "n=%lld points out of range", n);
+  MDF_REQUIRE((out && pts) || n == 0, "null pointer argument");
+  MDF_REQUIRE(matrix, "null pointer argument: matrix");
+  Affine m{};
+  for (int k = 0; k < 12; ++k) {
+    MDF_REQUIRE(std::isfinite(matrix[k]), "matrix entry %d is not finite", k);
+    m.r[k] = matrix[k];
+  }
+  if (n == 0) return MDF_OK;
+  hipLaunchKernelGGL(pts_transform_kernel, dim3(grid_of(n)), dim3(kBlock), 0, (hipStream_t)stream, out, pts, n, m);
+  return mdf::check_launch("pts_transform_kernel");
+}
+
+extern "C" int mdf_pts_crop(const double* pts, long long n, int axis, double axis_min, double axis_max, const double* polygon, int k,
+                            unsigned char* keep, void* stream) {
+  MDF_REQUIRE(n >= 0 && n < (1ll << 40), "n=%lld points out of range", n);
+  MDF_REQUIRE((pts && keep) || n == 0, "null pointer argument");
+  MDF_REQUIRE(axis >= 0 && axis <= 2, "axis=%d must be 0, 1 or 2", axis);
+  MDF_REQUIRE(k >= 3 && k <= kMaxPoly, "polygon of k=%d vertices: 3 <= k <= %d", k, kMaxPoly);
+  MDF_REQUIRE(polygon, "null pointer argument: polygon");
+  MDF_REQUIRE(!std::isnan(axis_min) && !std::isnan(axis_max), "axis_min / axis_max is NaN");
+  CropArgs a{};
+  a.pts = pts; a.n = n; a.axis = axis; a.k = k; a.amin = axis_min; a.amax = axis_max; a.keep = keep;
+  a.iu = axis == 0 ? 1 : 0;
+  a.iv = axis == 2 ? 1 : 2;
+  for (int e = 0; e < k; ++e) {
+    MDF_REQUIRE(std::isfinite(polygon[e * 2]) && std::isfinite(polygon[e * 2 + 1]), "polygon vertex %d is not finite", e);
+    a.poly[e][0] = polygon[e * 2];
+    a.poly[e][1] = polygon[e * 2 + 1];
+  }
+  if (n == 0) return MDF_OK;
+  hipLaunchKernelGGL(pts_crop_kernel, dim3(grid_of(n)), dim3(kBlock), 0, (hipStream_t)stream, a);
+  return mdf::check_launch("pts_crop_kernel");
+}
+
+extern "C" long long mdf_pts_voxel_workspace(long long n) {
+  if (n < 0 || n >= (1ll << 31) - kTile) return 0;
+  return voxel_layout(nullptr, n).bytes;
+}
+
+extern "C" int mdf_pts_voxel_downsample(const double* pts, const double* attrs, int nattr, long long n, double voxel, void* workspace,
+                                        long long ws_bytes, double* out_pts, double* out_attrs, int* out_count, long long* m,
+                                        void* stream) {
+  MDF_REQUIRE(n >= 0 && n < (1ll << 31) - kTile, "n=%lld points out of range", n);
+  MDF_REQUIRE(std::isfinite(voxel) && voxel > 0, "voxel=%g must be finite and > 0", voxel);
+  MDF_REQUIRE(nattr >= 0 && nattr <= 6, "nattr=%d attribute columns: 0..6", nattr);
+  MDF_REQUIRE(m, "null pointer argument: m");
+  MDF_REQUIRE((pts && out_pts && out_count) || n == 0, "null pointer argument");
+  MDF_REQUIRE((attrs && out_attrs) || nattr == 0 || n == 0, "null pointer argument: attrs");
+  MDF_REQUIRE(workspace, "null pointer argument: workspace");
+  MDF_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "workspace must be 16-byte aligned");
+  const long long need = voxel_layout(nullptr, n).bytes;
+  MDF_REQUIRE(ws_bytes >= need, "workspace too small: %lld bytes, %lld needed", ws_bytes, need);
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 0) {
+    if (hipMemsetAsync(m, 0, 8, s) != hipSuccess) return mdf::fail(MDF_EHIP, "hipMemsetAsync failed");
+    return MDF_OK;
+  }
+  const VoxelLayout L = voxel_layout(static_cast<char*>(workspace), n);
+  const int nbb = (int)std::min<long long>(kBboxBlocks, (n + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(pts_bbox_kernel, dim3(nbb), dim3(kBlock), 0, s, pts, n, L.bbox_part);
+  if (int rc = mdf::check_launch("pts_bbox_kernel")) return rc;
+  hipLaunchKernelGGL(pts_bbox_final_kernel, dim3(1), dim3(64), 0, s, L.bbox_part, nbb, L.bbox);
+  if (int rc = mdf::check_launch("pts_bbox_final_kernel")) return rc;
+  hipLaunchKernelGGL(pts_vox_key_kernel, dim3(grid_of(n)), dim3(kBlock), 0, s, pts, n, L.bbox, voxel, L.key0, L.val0, L.ctl);
+  if (int rc = mdf::check_launch("pts_vox_key_kernel")) return rc;
+  unsigned long long *kin = L.key0, *kout = L.key1;
+  int *vin = L.val0, *vout = L.val1;
+  for (int shift = 0; shift < 64; shift += 8) {
+    hipLaunchKernelGGL(pts_sort_hist_kernel, dim3((unsigned)L.ntiles), dim3(kBlock), 0, s, kin, n, shift, L.ntiles, L.hist);
+    if (int rc = mdf::check_launch("pts_sort_hist_kernel")) return rc;
+    hipLaunchKernelGGL(pts_sort_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, L.hist, kRadix * L.ntiles, L.hoff, nullptr);
+    if (int rc = mdf::check_launch("pts_sort_scan_kernel")) return rc;
+    hipLaunchKernelGGL(pts_sort_scatter_kernel, dim3((unsigned)L.ntiles), dim3(kBlock), 0, s, kin, vin, n, shift, L.ntiles, L.hoff, kout,
+                       vout);
+    if (int rc = mdf::check_launch("pts_sort_scatter_kernel")) return rc;
+    std::swap(kin, kout);
+    std::swap(vin, vout);
+  }
+  hipLaunchKernelGGL(pts_vox_chunk_sum_kernel, dim3((unsigned)L.nchunks), dim3(kBlock), 0, s, kin, n, L.chunk_sums);
+  if (int rc = mdf::check_launch("pts_vox_chunk_sum_kernel")) return rc;
+  hipLaunchKernelGGL(pts_sort_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, L.chunk_sums, L.nchunks, L.chunk_off, L.total);
+  if (int rc = mdf::check_launch("pts_sort_scan_kernel")) return rc;
+  hipLaunchKernelGGL(pts_vox_offsets_kernel, dim3((unsigned)L.nchunks), dim3(kBlock), 0, s, kin, n, L.chunk_off, L.seg_start);
+  if (int rc = mdf::check_launch("pts_vox_offsets_kernel")) return rc;
+  VoxMeanArgs a{pts, attrs, nattr, n, vin, L.seg_start, L.total, L.ctl, out_pts, out_attrs, out_count, m};
+  hipLaunchKernelGGL(pts_vox_mean_kernel, dim3(grid_of(n)), dim3(kBlock), 0, s, a);
+  return mdf::check_launch("pts_vox_mean_kernel");
+}
+
+extern "C" long long mdf_pts_icp_workspace(void) { return align16((long long)kIcpBlocks * kIcpVals * 8); }
+
+extern "C" int mdf_pts_icp_sums(const double* src, long long n, const double* tgt, long long nt, const int* nearest, const double* d2,
+                                double threshold, void* workspace, long long ws_bytes, double* out, void* stream) {
+  MDF_REQUIRE(n >= 0 && n < (1ll << 40) && nt >= 0 && nt < (1ll << 31), "n=%lld / nt=%lld out of range", n, nt);
+  MDF_REQUIRE((src && nearest && d2) || n == 0, "null pointer argument (source side)");
+  MDF_REQUIRE(tgt || nt == 0, "null pointer argument: tgt");
+  MDF_REQUIRE(out && workspace, "null pointer argument: out / workspace");
+  MDF_REQUIRE(std::isfinite(threshold) && threshold > 0, "threshold=%g must be finite and > 0", threshold);
+  MDF_REQUIRE(ws_bytes >= mdf_pts_icp_workspace(), "workspace too small: %lld bytes, %lld needed", ws_bytes, mdf_pts_icp_workspace());
+  IcpArgs a{src, tgt, nearest, d2, n, nt, sqrt_ge_bound(threshold), static_cast<double*>(workspace), out};
+  const int nb = (int)std::max<long long>(1, std::min<long long>(kIcpBlocks, (n + kBlock - 1) / kBlock));
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(pts_icp_moment_kernel<false>, dim3(nb), dim3(kBlock), 0, s, a);
+  if (int rc = mdf::check_launch("pts_icp_moment_kernel")) return rc;
+  hipLaunchKernelGGL(pts_icp_final_kernel<false>, dim3(1), dim3(kBlock), 0, s, a.part, nb, out);
+  if (int rc = mdf::check_launch("pts_icp_final_kernel")) return rc;
+  hipLaunchKernelGGL(pts_icp_moment_kernel<true>, dim3(nb), dim3(kBlock), 0, s, a);
+  if (int rc = mdf::check_launch("pts_icp_moment_kernel")) return rc;
+  hipLaunchKernelGGL(pts_icp_final_kernel<true>, dim3(1), dim3(kBlock), 0, s, a.part, nb, out);
+  return mdf::check_launch("pts_icp_final_kernel");
 }

@@ -75,6 +75,13 @@ SIGNATURES = {
     "mdf_pts_reduce": (c_int, [c_fp, c_i64, c_i64, c_fp, ctypes.c_double, c_fp, c_i64, c_fp, c_i64, c_int, c_int, c_fp, c_fp, c_fp]),
     "mdf_dtu_masks": (c_int, [c_fp, c_i64, c_fp, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_double, c_fp, c_fp,
                               c_i64, ctypes.POINTER(ctypes.c_double), c_fp, c_fp]),
+    "mdf_pts_nn": (c_int, [c_fp, c_i64, c_i64, c_fp, c_fp, c_i64, c_i64, ctypes.c_double, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "mdf_pts_transform": (c_int, [c_fp, c_fp, c_i64, ctypes.POINTER(ctypes.c_double), c_fp]),
+    "mdf_pts_crop": (c_int, [c_fp, c_i64, c_int, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_double), c_int, c_fp, c_fp]),
+    "mdf_pts_voxel_workspace": (c_i64, [c_i64]),
+    "mdf_pts_voxel_downsample": (c_int, [c_fp, c_fp, c_int, c_i64, ctypes.c_double, c_fp, c_i64, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "mdf_pts_icp_workspace": (c_i64, []),
+    "mdf_pts_icp_sums": (c_int, [c_fp, c_i64, c_fp, c_i64, c_fp, c_fp, ctypes.c_double, c_fp, c_i64, c_fp, c_fp]),
     "mdf_bn_stats_fwd": (c_int, [c_fp, c_i64, c_int, c_int, c_fp, c_fp]),
     "mdf_bn_finalize_fwd": (c_int, [c_fp, c_fp, c_fp, ctypes.c_float, ctypes.c_float, c_i64, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_fp]),
     "mdf_bn_relu_apply_fwd": (c_int, [c_fp, c_fp, c_fp, c_fp, c_i64, c_int, c_int, c_fp]),
@@ -164,3 +171,9 @@ def dtu_eval_scan(*args, **kwargs):
     """DTU point-cloud evaluation of one scan (ops.dtu_eval_scan; the reference's BaseEvalMain_web.m / PointCompareMain.m)."""
     from .ops import dtu_eval_scan as _dtu_eval_scan
     return _dtu_eval_scan(*args, **kwargs)
+
+
+def tanks_eval_scene(*args, **kwargs):
+    """Tanks and Temples F-score of one scene (ops.tanks_eval_scene; the training scenes' offline protocol)."""
+    from .ops import tanks_eval_scene as _tanks_eval_scene
+    return _tanks_eval_scene(*args, **kwargs)

@@ -59,6 +59,10 @@ KERNEL_FAMILY = {
     "pts_node_kernel": POINT_EVAL, "pts_nn_kernel": POINT_EVAL, "pts_rank_kernel": POINT_EVAL, "pts_radius_kernel": POINT_EVAL,
     "pts_reduce_init_kernel": POINT_EVAL, "pts_reduce_round_kernel": POINT_EVAL, "pts_reduce_step_kernel": POINT_EVAL,
     "pts_reduce_keep_kernel": POINT_EVAL, "pts_dtu_masks_kernel": POINT_EVAL,
+    # point_eval.hip (Tanks and Temples evaluation: nearest index, transform, crop volume, voxel grid, ICP sums)
+    "pts_nn_idx_kernel": POINT_EVAL, "pts_transform_kernel": POINT_EVAL, "pts_crop_kernel": POINT_EVAL, "pts_vox_key_kernel": POINT_EVAL,
+    "pts_vox_chunk_sum_kernel": POINT_EVAL, "pts_vox_offsets_kernel": POINT_EVAL, "pts_vox_mean_kernel": POINT_EVAL,
+    "pts_icp_moment_kernel": POINT_EVAL, "pts_icp_final_kernel": POINT_EVAL,
     # loss.hip
     "masked_smooth_l1_reduce_kernel": CONTROL, "masked_smooth_l1_finalize_kernel": CONTROL, "masked_smooth_l1_bwd_kernel": CONTROL,
     "masked_smooth_l1_reduce_multi_kernel": CONTROL, "masked_smooth_l1_bwd_multi_kernel": CONTROL, "adam_step_kernel": CONTROL,

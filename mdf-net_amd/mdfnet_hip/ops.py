@@ -1069,3 +1069,286 @@ def dtu_eval_scan(qdata, qstl, obs_mask, bb, res, plane, dst=0.2, seed=0, max_di
           "Rounds": stats["rounds"], "Edges": stats["edges"]}
     ev.update(dtu_scan_stats(ev, max_dist))
     return ev
+
+
+# --------------------------------------------------------------------------- Tanks and Temples F-score evaluation
+# The training scenes' offline protocol: initial alignment from the camera centres, crop volume, voxel-grid
+# downsampling, three rounds of point-to-point ICP, precision / recall / F at the scene's distance tau.  Everything fp64.
+TANKS_TAU = {"Barn": 0.01, "Caterpillar": 0.005, "Church": 0.025, "Courthouse": 0.025, "Ignatius": 0.003, "Meetingroom": 0.01,
+             "Truck": 0.005}
+TANKS_ICP_ITERS = 20
+TANKS_ICP_REL = 1e-6                    # stop when fitness and inlier RMSE both change by less than this, relatively
+TANKS_STAGE_C_POINTS = 4e6              # stage C keeps every k-th cropped point, k = max(round(n / 4e6), 1)
+TANKS_HIST_BINS, TANKS_HIST_STRETCH = 100, 5
+VOXEL_MAX_ATTRS = 6
+
+
+def _mat4(T):
+    import numpy as np
+    T = np.ascontiguousarray(np.asarray(T.cpu() if torch.is_tensor(T) else T, dtype=np.float64))
+    if T.shape != (4, 4) or not np.isfinite(T).all():
+        raise ValueError("a finite 4x4 matrix is expected")
+    return T
+
+
+def nn_search(index, queries, cap, return_d2=False, return_visits=False):
+    """Exact nearest neighbour of every query among the index's points (mdf_pts_nn): -> (dist [m] fp64, nearest [m] int32) on the
+    GPU, nearest = the point's position in the array the index was built from, or -1 (and dist = cap) when no point lies within
+    d < cap; ties on d^2 go to the lowest position.  queries: GPU [m,3] or a PointIndex (walked in Morton order, results at the
+    input positions).  return_d2 appends d^2 (+inf when none), return_visits the leaves visited per query."""
+    if not isinstance(index, PointIndex):
+        raise TypeError("nn_search: index must come from point_index()")
+    if isinstance(queries, PointIndex):
+        m, qidx, qpts, qbytes = queries.n, queries.buf.data_ptr(), None, queries.nbytes
+    else:
+        _need_gpu(queries)
+        q = _pts64(queries)
+        m, qidx, qpts, qbytes = q.shape[0], None, q.data_ptr(), 0
+    dev = index.device
+    dist = torch.empty(m, device=dev, dtype=torch.float64)
+    d2 = torch.empty(m, device=dev, dtype=torch.float64) if return_d2 else None
+    nearest = torch.empty(m, device=dev, dtype=torch.int32)
+    visits = torch.empty(m, device=dev, dtype=torch.int32) if return_visits else None
+    if m:
+        _abi("mdf_pts_nn", (index.buf.data_ptr(), index.n, index.nbytes, qidx, qpts, m, qbytes, ctypes.c_double(float(cap)),
+                            dist.data_ptr(), d2.data_ptr() if return_d2 else None, nearest.data_ptr(),
+                            visits.data_ptr() if return_visits else None, _stream(dist)),
+             tag=f"n{index.n} m{m}", work={"queries": float(m), "bound": "valu"})
+    return (dist, nearest) + ((d2,) if return_d2 else ()) + ((visits,) if return_visits else ())
+
+
+def transform_points(pts, T):
+    """p' = T p for a host 4x4 matrix (rows 0..2 are applied): x' = ((t00 x + t01 y) + t02 z) + t03.  pts GPU [n,3] -> [n,3] fp64."""
+    _need_gpu(pts)
+    pts = _pts64(pts)
+    n = pts.shape[0]
+    out = torch.empty_like(pts)
+    _abi("mdf_pts_transform", (out.data_ptr() if n else None, pts.data_ptr() if n else None, n, _host_doubles(_mat4(T), 16),
+                               _stream(pts)), tag=f"n{n}", work={"bytes": 48.0 * n, "bound": "hbm"})
+    return out
+
+
+def crop_volume(pts, axis, axis_min, axis_max, polygon):
+    """The crop-volume test (mdf_pts_crop): keep [n] bool GPU, True iff axis_min <= p[axis] <= axis_max and the point's other two
+    coordinates (u, v) = (y, z) / (x, z) / (x, y) for axis 0 / 1 / 2 lie inside `polygon` [k,2] (3 <= k <= 64) by the even-odd
+    rule of include/mdfnet_hip.h."""
+    import numpy as np
+    _need_gpu(pts)
+    pts = _pts64(pts)
+    n = pts.shape[0]
+    poly = np.ascontiguousarray(np.asarray(polygon, dtype=np.float64))
+    if poly.ndim != 2 or poly.shape[1] != 2:
+        raise ValueError(f"polygon must be [k,2], got {poly.shape}")
+    k = poly.shape[0]
+    keep = torch.empty(max(n, 1), device=pts.device, dtype=torch.uint8)
+    _abi("mdf_pts_crop", (pts.data_ptr() if n else None, n, int(axis), ctypes.c_double(float(axis_min)), ctypes.c_double(float(axis_max)),
+                          _host_doubles(poly, 2 * k) if k else None, k, keep.data_ptr(), _stream(pts)), tag=f"n{n} k{k}",
+         work={"points": float(n), "bound": "valu"})
+    return keep[:n].bool()
+
+
+def voxel_downsample(pts, voxel, attrs=None, return_counts=False):
+    """Voxel-grid downsampling (mdf_pts_voxel_downsample): one point per occupied cell of side `voxel`, the mean of the cell's
+    points summed in input order, cells in ascending (x, y, z) cell order with the grid's origin at min(pts) - voxel/2.
+    attrs: up to 6 fp64 columns [n,k] (colours, normals) averaged the same way.
+    -> pts [m,3] (, attrs [m,k] when given) (, counts [m] int32 with return_counts), on the GPU."""
+    _need_gpu(pts, attrs)
+    pts = _pts64(pts)
+    n = pts.shape[0]
+    dev = pts.device
+    voxel = float(voxel)
+    if not (voxel > 0 and voxel < float("inf")):
+        raise ValueError(f"voxel={voxel} must be finite and > 0")
+    k = 0
+    if attrs is not None:
+        k = attrs.shape[-1] if attrs.dim() > 1 else 1
+        attrs = attrs.to(torch.float64).reshape(n, k).contiguous()
+        if k > VOXEL_MAX_ATTRS:
+            raise ValueError(f"{k} attribute columns: at most {VOXEL_MAX_ATTRS}")
+    nbytes = int(lib().mdf_pts_voxel_workspace(n))
+    if nbytes <= 0 and n:
+        raise ValueError(f"voxel_downsample: {n} points are too many")
+    ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    out = torch.empty((max(n, 1), 3), device=dev, dtype=torch.float64)
+    oat = torch.empty((max(n, 1), max(k, 1)), device=dev, dtype=torch.float64)
+    cnt = torch.empty(max(n, 1), device=dev, dtype=torch.int32)
+    m = torch.zeros(1, device=dev, dtype=torch.int64)
+    _abi("mdf_pts_voxel_downsample", (pts.data_ptr() if n else None, attrs.data_ptr() if k and n else None, k, n, ctypes.c_double(voxel),
+                                      ws.data_ptr(), ws.numel(), out.data_ptr(), oat.data_ptr(), cnt.data_ptr(), m.data_ptr(),
+                                      _stream(pts)), tag=f"n{n} a{k}", work={"points": float(n), "bound": "hbm"})
+    m = int(m.item())
+    if m < 0:
+        raise ValueError(f"voxel_downsample: voxel={voxel} needs more than 2^21 cells on an axis")
+    res = (out[:m].clone(),)
+    if attrs is not None:
+        res += (oat[:m, :k].clone(),)
+    if return_counts:
+        res += (cnt[:m].clone(),)
+    return res[0] if len(res) == 1 else res
+
+
+def icp_sums(src, tgt, nearest, d2, threshold):
+    """The sums of one point-to-point ICP step (mdf_pts_icp_sums) over the pairs (src[i], tgt[nearest[i]]) with nearest[i] >= 0 and
+    sqrt(d2[i]) < threshold -> host numpy [17]: inlier count, sum of d^2, source centroid, target centroid, H (3x3 row-major,
+    H[a][b] = sum (s_a - cs_a)(t_b - ct_b))."""
+    _need_gpu(src, tgt, nearest, d2)
+    src, tgt = _pts64(src), _pts64(tgt)
+    n, nt = src.shape[0], tgt.shape[0]
+    nearest = nearest.to(torch.int32).contiguous()
+    d2 = d2.to(torch.float64).contiguous()
+    if nearest.numel() != n or d2.numel() != n:
+        raise ValueError(f"{nearest.numel()} matches / {d2.numel()} distances for {n} source points")
+    ws = torch.empty(int(lib().mdf_pts_icp_workspace()), device=src.device, dtype=torch.uint8)
+    out = torch.zeros(17, device=src.device, dtype=torch.float64)
+    _abi("mdf_pts_icp_sums", (src.data_ptr() if n else None, n, tgt.data_ptr() if nt else None, nt, nearest.data_ptr() if n else None,
+                              d2.data_ptr() if n else None, ctypes.c_double(float(threshold)), ws.data_ptr(), ws.numel(), out.data_ptr(),
+                              _stream(src)), tag=f"n{n}", work={"points": float(n), "bound": "latency"})
+    return out.cpu().numpy()
+
+
+def icp_rigid_update(sums):
+    """The rigid motion that best maps the inlier source points onto their matches (host, numpy): from the centroids and the
+    cross-covariance H of icp_sums, R = V diag(1, 1, det(V U^T)) U^T with H = U S V^T, t = ct - R cs.  -> 4x4."""
+    import numpy as np
+    cs, ct, H = sums[2:5], sums[5:8], np.asarray(sums[8:17], dtype=np.float64).reshape(3, 3)
+    U, _, Vt = np.linalg.svd(H)
+    D = np.diag([1.0, 1.0, 1.0 if np.linalg.det(Vt.T @ U.T) >= 0 else -1.0])
+    R = Vt.T @ D @ U.T
+    T = np.eye(4)
+    T[:3, :3] = R
+    T[:3, 3] = ct - R @ cs
+    return T
+
+
+def _rel_small(a, b, tol):
+    return abs(a - b) < tol * max(abs(b), 1e-300)
+
+
+def icp_point_to_point(source, target, threshold, init=None, max_iter=TANKS_ICP_ITERS, rel_tol=TANKS_ICP_REL, target_index=None):
+    """Point-to-point ICP without scale.  The source under T is matched to its exact nearest target points with d < threshold;
+    fitness = inliers / source points, rmse = sqrt(mean d^2 over inliers).  Then, up to max_iter times: T <- dT T with dT the
+    rigid update of the matches (icp_rigid_update), match again, and stop once fitness and rmse both changed by less than rel_tol
+    relatively (or no inlier is left).  source, target: GPU [n,3]; target_index: a PointIndex over target to reuse.
+    -> (T 4x4 host numpy, fitness, rmse, iterations = updates applied)."""
+    import numpy as np
+    _need_gpu(source, target)
+    src, tgt = _pts64(source), _pts64(target)
+    index = target_index if target_index is not None else point_index(tgt)
+    if index.n != tgt.shape[0]:
+        raise ValueError(f"index over {index.n} points for {tgt.shape[0]} target points")
+    n = src.shape[0]
+    T = np.eye(4) if init is None else _mat4(init).copy()
+
+    def evaluate(T):
+        cur = transform_points(src, T)
+        _, nearest, d2 = nn_search(index, cur, threshold, return_d2=True)
+        s = icp_sums(cur, tgt, nearest, d2, threshold)
+        cnt = s[0]
+        return s, (cnt / n if n else 0.0), (float(np.sqrt(s[1] / cnt)) if cnt > 0 else 0.0)
+
+    sums, fitness, rmse = evaluate(T)
+    it = 0
+    while it < max_iter and sums[0] > 0:
+        T = icp_rigid_update(sums) @ T
+        it += 1
+        pf, pr = fitness, rmse
+        sums, fitness, rmse = evaluate(T)
+        if _rel_small(fitness, pf, rel_tol) and _rel_small(rmse, pr, rel_tol):
+            break
+    return T, float(fitness), float(rmse), it
+
+
+def umeyama(src, dst, with_scale=True):
+    """The least-squares similarity (Umeyama 1991) mapping src [n,3] onto dst [n,3] (host): -> 4x4 with c R and t."""
+    import numpy as np
+    src, dst = np.asarray(src, dtype=np.float64).reshape(-1, 3), np.asarray(dst, dtype=np.float64).reshape(-1, 3)
+    if len(src) != len(dst) or len(src) < 3:
+        raise ValueError(f"umeyama: {len(src)} and {len(dst)} points (equal counts, at least 3)")
+    ms, md = src.mean(0), dst.mean(0)
+    a, b = src - ms, dst - md
+    cov = b.T @ a / len(src)
+    U, S, Vt = np.linalg.svd(cov)
+    D = np.diag([1.0, 1.0, 1.0 if np.linalg.det(U) * np.linalg.det(Vt) >= 0 else -1.0])
+    R = U @ D @ Vt
+    c = float((S * np.diag(D)).sum() / (a * a).sum() * len(src)) if with_scale else 1.0
+    T = np.eye(4)
+    T[:3, :3] = c * R
+    T[:3, 3] = md - c * R @ ms
+    return T
+
+
+def tanks_initial_alignment(est_poses, ref_poses, trans):
+    """Step 1 of the protocol (host): the similarity that maps the camera centres of the estimate's trajectory onto those of the
+    reference trajectory after `trans`, least squares over all cameras.  est_poses, ref_poses: [n,4,4] camera-to-world."""
+    import numpy as np
+    est = np.asarray(est_poses, dtype=np.float64).reshape(-1, 4, 4)
+    ref = np.asarray(ref_poses, dtype=np.float64).reshape(-1, 4, 4)
+    if len(est) != len(ref):
+        raise ValueError(f"the estimate's trajectory has {len(est)} cameras, the reference {len(ref)}")
+    trans = _mat4(trans)
+    ref_c = ref[:, :3, 3] @ trans[:3, :3].T + trans[:3, 3]
+    return umeyama(est[:, :3, 3], ref_c, with_scale=True)
+
+
+def tanks_fscore(d_est, d_gt, tau):
+    """Step 6's numbers from the two distance arrays (host): precision, recall, F and the two cumulative histograms."""
+    import numpy as np
+    d_est, d_gt = np.asarray(d_est, dtype=np.float64), np.asarray(d_gt, dtype=np.float64)
+    p = float((d_est < tau).mean()) if d_est.size else 0.0
+    r = float((d_gt < tau).mean()) if d_gt.size else 0.0
+    f = 2 * p * r / (p + r) if p + r > 0 else 0.0
+    top = TANKS_HIST_STRETCH * tau
+    hists = []
+    for d in (d_est, d_gt):
+        h, edges = np.histogram(d, bins=TANKS_HIST_BINS, range=(0.0, top))
+        hists.append(np.cumsum(h).astype(np.float64) / max(d.size, 1))
+    return p, r, f, hists[0], hists[1], edges
+
+
+def tanks_eval_scene(est, gt, crop, tau, init, device=None):
+    """The Tanks and Temples F-score of one scene on the GPU.  est [N,3], gt [M,3]: host arrays or GPU tensors; crop: dict with
+    axis (0/1/2), axis_min, axis_max, polygon [k,2] (tools/data_io.py:read_crop_json); tau: the scene's distance; init: the 4x4
+    of step 1.  Stages A, B (voxel tau, tau/2; ICP threshold 80 tau, 20 tau) and C (every k-th cropped point; 2 tau) refine T
+    against the whole ground truth; then both clouds are cropped, downsampled at tau/2 and compared.
+    -> dict: precision, recall, fscore, tau, T, T_init, stage_T [3,4,4], stage_fitness / stage_rmse / stage_iterations [3],
+    hist_est, hist_gt [100] (cumulative, over [0, 5 tau]), hist_edges [101] and the point counts n_*."""
+    import numpy as np
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    e, g = _pts64(est, dev), _pts64(gt, dev)
+    tau = float(tau)
+    if not (tau > 0 and np.isfinite(tau)):
+        raise ValueError(f"tau={tau} must be finite and > 0")
+    T = _mat4(init).copy()
+    res = {"tau": tau, "T_init": T.copy(), "n_est": e.shape[0], "n_gt": g.shape[0]}
+
+    def cropped(pts):
+        return pts[crop_volume(pts, crop["axis"], crop["axis_min"], crop["axis_max"], crop["polygon"])].contiguous()
+
+    gidx = point_index(g)
+    stage_T, stage_f, stage_r, stage_i = [], [], [], []
+    for name, vox, thr in (("A", tau, 80 * tau), ("B", tau / 2, 20 * tau), ("C", None, 2 * tau)):
+        s = cropped(transform_points(e, T))
+        res[f"n_crop_{name}"] = s.shape[0]
+        if vox is not None:
+            s = voxel_downsample(s, vox)
+        else:
+            k = max(int(round(s.shape[0] / TANKS_STAGE_C_POINTS)), 1)
+            s = s[::k].contiguous()
+        res[f"n_down_{name}"] = s.shape[0]
+        dT, fit, rmse, its = icp_point_to_point(s, g, thr, target_index=gidx)
+        T = dT @ T
+        stage_T.append(T.copy()); stage_f.append(fit); stage_r.append(rmse); stage_i.append(its)
+    del gidx
+    ec = cropped(transform_points(e, T))
+    gc = cropped(g)
+    ed, gd = voxel_downsample(ec, tau / 2), voxel_downsample(gc, tau / 2)
+    res.update(n_est_crop=ec.shape[0], n_gt_crop=gc.shape[0], n_est_down=ed.shape[0], n_gt_down=gd.shape[0])
+    cap = 2 * TANKS_HIST_STRETCH * tau                    # past the histograms' range: a capped distance lands in no bin
+    eidx, gdx = point_index(ed), point_index(gd)
+    d1 = nn_search(gdx, eidx, cap)[0].cpu().numpy()
+    d2 = nn_search(eidx, gdx, cap)[0].cpu().numpy()
+    p, r, f, h1, h2, edges = tanks_fscore(d1, d2, tau)
+    res.update(precision=p, recall=r, fscore=f, T=T, stage_T=np.stack(stage_T), stage_fitness=np.array(stage_f),
+               stage_rmse=np.array(stage_r), stage_iterations=np.array(stage_i, dtype=np.int64), hist_est=h1, hist_gt=h2,
+               hist_edges=edges, dist_est=d1, dist_gt=d2)
+    return res

@@ -333,3 +333,73 @@ def write_mat(path, arrays):
         np.array([0x0100], dtype="<u2").tobytes() + b"IM"
     with open(path, "wb") as f:
         f.write(head + body)
+
+
+# --------------------------------------------------------------------------- Tanks and Temples evaluation files
+_AXES = "XYZ"
+
+
+def read_trajectory_log(path):
+    """A trajectory .log: per camera a line of three integers (`i i 0`) and the 4 rows of its camera-to-world matrix
+    -> poses [n,4,4] float64."""
+    with open(path) as f:
+        rows = [ln.split() for ln in f if ln.strip()]
+    if len(rows) % 5:
+        raise ValueError(f"{path}: {len(rows)} non-empty lines, not a multiple of 5")
+    poses = []
+    for c in range(0, len(rows), 5):
+        if len(rows[c]) != 3 or any(len(r) != 4 for r in rows[c + 1:c + 5]):
+            raise ValueError(f"{path}: malformed camera block at line {c + 1}")
+        poses.append([[float(x) for x in r] for r in rows[c + 1:c + 5]])
+    return np.array(poses, dtype=np.float64).reshape(-1, 4, 4)
+
+
+def write_trajectory_log(path, poses):
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    with open(path, "w") as f:
+        for i, p in enumerate(poses):
+            f.write(f"{i} {i} 0\n")
+            for r in p:
+                f.write(" ".join(repr(float(x)) for x in r) + "\n")
+
+
+def read_matrix_txt(path):
+    """A 4x4 matrix as text (whitespace-separated, 4 rows) -> [4,4] float64."""
+    m = np.loadtxt(path, dtype=np.float64)
+    if m.shape != (4, 4):
+        raise ValueError(f"{path}: a 4x4 matrix is expected, got {m.shape}")
+    return m
+
+
+def write_matrix_txt(path, m):
+    m = np.asarray(m, dtype=np.float64).reshape(4, 4)
+    with open(path, "w") as f:
+        for r in m:
+            f.write(" ".join(repr(float(x)) for x in r) + "\n")
+
+
+def crop_uv_axes(axis):
+    """The two axes the crop polygon lives on, for an orthogonal axis 0 / 1 / 2: (y, z), (x, z), (x, y)."""
+    return (1 if axis == 0 else 0), (1 if axis == 2 else 2)
+
+
+def read_crop_json(path):
+    """A crop volume (.json: orthogonal_axis "X"/"Y"/"Z", axis_min, axis_max, bounding_polygon [[x,y,z], ...]) -> dict with
+    axis (0/1/2), axis_min, axis_max, polygon [k,2] (the polygon's coordinates on crop_uv_axes(axis)) and polygon3 [k,3]."""
+    import json
+    with open(path) as f:
+        j = json.load(f)
+    axis = _AXES.index(str(j["orthogonal_axis"]).upper())
+    poly3 = np.asarray(j["bounding_polygon"], dtype=np.float64).reshape(-1, 3)
+    iu, iv = crop_uv_axes(axis)
+    return {"axis": axis, "axis_min": float(j["axis_min"]), "axis_max": float(j["axis_max"]),
+            "polygon": np.ascontiguousarray(poly3[:, [iu, iv]]), "polygon3": poly3}
+
+
+def write_crop_json(path, axis, axis_min, axis_max, polygon3):
+    import json
+    poly3 = np.asarray(polygon3, dtype=np.float64).reshape(-1, 3)
+    j = {"axis_max": float(axis_max), "axis_min": float(axis_min), "bounding_polygon": [[float(x) for x in p] for p in poly3],
+         "class_name": "SelectionPolygonVolume", "orthogonal_axis": _AXES[int(axis)], "version_major": 1, "version_minor": 0}
+    with open(path, "w") as f:
+        json.dump(j, f, indent=1)
