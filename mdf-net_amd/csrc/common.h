@@ -40,6 +40,11 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nblk) {
 // level 0; after every 16 elements level 0 is folded into level 1 (after every 256 into level 2, ...); the
 // result is ((l0 + l1) + l2) + l3.  Mirroring it makes `torch.sum(a*b, dim)`-style reductions bit-identical
 // to the reference's CPU result for the same inputs (verified against the goldens for D = 8, 24, 48).
+// Scope of that claim: this is the order of ATen's VECTORISED outer-sum path, which covers every pixel only when the
+// flattened h*w axis is a multiple of four SIMD vectors of the reference's host (32 floats with AVX2, 64 with AVX-512).
+// The tail pixels of any other map go through a 4-way interleaved row sum there and differ in the last bits, so
+// live torch has no single order.  Everywhere else this order IS the definition: tests/heads_mirror.py:cascade_sum
+// states it, tests/test_heads_mirror_cpu.py ties it to the goldens, and other shapes are held to float64 bounds.
 struct CascadeSum {
   float l0 = 0.f, l1 = 0.f, l2 = 0.f, l3 = 0.f;
   unsigned n = 0;

@@ -353,8 +353,11 @@ def hypos_fit(mode, prob, depth, depth_hypos, fit_row=None):
     prob = _f32c(prob)
     hyp, pp = _hypos_arg(depth_hypos, h, w)
     out = torch.empty((b, h, w), device=prob.device, dtype=torch.float32)
-    _abi("mdf_hypos_fit_fwd", (mode, prob.data_ptr(), None if depth is None else _f32c(depth).data_ptr(),
-                                  hyp.data_ptr(), pp, None if fit_row is None else _f32c(fit_row).data_ptr(),
+    # (locals: a converted copy freed before the enqueue hands its block to the next conversion, which then overwrites it)
+    depth_c = None if depth is None else _f32c(depth)
+    row_c = None if fit_row is None else _f32c(fit_row)
+    _abi("mdf_hypos_fit_fwd", (mode, prob.data_ptr(), None if depth_c is None else depth_c.data_ptr(),
+                                  hyp.data_ptr(), pp, None if row_c is None else row_c.data_ptr(),
                                   out.data_ptr(), b, d, h, w, _stream(out),))
     return out
 
@@ -365,8 +368,9 @@ def hypos_from_fit(mode, s, depth, depth_range_f32, log_thresh, ndepths, upsampl
     b, h, w = s.shape
     ho, wo = (2 * h, 2 * w) if upsample else (h, w)
     out = torch.empty((b, ndepths, ho, wo), device=s.device, dtype=torch.float32)
-    _abi("mdf_hypos_from_fit_fwd", (mode, _f32c(s).data_ptr(), _f32c(depth).data_ptr(),
-                                       _f32c(depth_range_f32).data_ptr(), ctypes.c_float(log_thresh), out.data_ptr(),
+    s_c, depth_c, range_c = _f32c(s), _f32c(depth), _f32c(depth_range_f32)      # (locals: as in hypos_fit)
+    _abi("mdf_hypos_from_fit_fwd", (mode, s_c.data_ptr(), depth_c.data_ptr(),
+                                       range_c.data_ptr(), ctypes.c_float(log_thresh), out.data_ptr(),
                                        b, ndepths, h, w, int(upsample), _stream(out),))
     return out
 
