@@ -436,6 +436,16 @@ int mdf_wgrad_sum_batch(const float* const* slabs, float* const* outs, const int
  * of a group as ONE launch (job table in the kernel arguments).  Results are those of the separate launches bit for bit.       */
 int mdf_wgrad_batch_begin(void);
 int mdf_wgrad_batch_flush(void* stream);
+/* Read-only: what the calling thread's last weight-gradient dispatch decided (a dispatch that mdf_wgrad_batch_begin only recorded
+ * counts), so that a test can tell which kernel form and tiling a shape took.  Copies min(n, MDF_WGRAD_PLAN_FIELDS) ints to `out`:
+ *     form, R, TH, tv, n_tiles, gx, gy, gz, split
+ * form: 0 wgrad_lds_kernel, 1 wgrad_kernel, 2 wgrad_a1_kernel, 3 wgrad_a1_valu_kernel, 4 wgrad2d_kernel (-1 before the first dispatch).
+ * LDS form: tap packing R, rows TH and voxels tv of a tile, the launch's tiles.  The direct forms report R = 0, TH = 1, the voxels one
+ * work item covers as tv (a 16-voxel chunk; the voxels a block of the vector-ALU form takes per iteration) and their item count as
+ * n_tiles.  gx = partial-tile slabs written, (gx, gy, gz) the grid, split the waves that share a channel-tile pair.  Returns
+ * MDF_WGRAD_PLAN_FIELDS.  Launches nothing.                                                                                      */
+#define MDF_WGRAD_PLAN_FIELDS 9
+int mdf_wgrad_last_plan(int* out, int n);
 /* (input gradients of these layers are mdf_conv3d_fwd with re-packed weights: a stride-1 conv with flipped taps and
  *  swapped channels, the transposed conv for a stride-2 conv and vice versa.) */
 

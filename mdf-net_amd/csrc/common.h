@@ -9,6 +9,7 @@ namespace mdf {
 
 void set_error(const char* fmt, ...);
 void note_launch(const char* kernel);     // abi.cpp: the kernel the calling thread enqueued last (mdf_last_launch)
+void note_wgrad_plan(int form, int R, int TH, int tv, long long n_tiles, int gx, int gy, int gz, int split);   // abi.cpp: mdf_wgrad_last_plan
 
 inline int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 inline int fail(int code, const char* fmt, ...) {

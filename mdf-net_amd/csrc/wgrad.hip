@@ -604,9 +604,11 @@ static int conv3d_wgrad_impl(const float* small_, const float* big, float* dw, f
     if (g > 512) g = 512;                                            // ... and two blocks per CU (r03 sweep: 256 / 512 / 1024 / 2048 blocks -> 48 / 25 / 30 / 36 us @8x288x384: the per-block reduction)
     if (g > gx) g = gx;                                              // (the workspace holds gx slabs)
     gx_used = (int)g;
+    mdf::note_wgrad_plan(3, 0, 1, (int)vpb, ((long long)B * Ds * Hs * Ws + vpb - 1) / vpb, gx_used, 1, 1, 1);
     if (Bc == 8) hipLaunchKernelGGL(wgrad_a1_valu_kernel<8>, dim3(gx_used), dim3(256), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(wgrad_a1_valu_kernel<16>, dim3(gx_used), dim3(256), 0, (hipStream_t)stream, p);
   } else if (A == 1 && Bc <= 16 && stride == 1) {
+    mdf::note_wgrad_plan(2, 0, 1, 16, p.n_items, gx, 1, 3, 4);
     hipLaunchKernelGGL(wgrad_a1_kernel, dim3(gx, 1, 3), dim3(256), 0, (hipStream_t)stream, p);
   } else {
     if (wgrad_use_lds()) {
@@ -616,6 +618,7 @@ static int conv3d_wgrad_impl(const float* small_, const float* big, float* dw, f
     }
     if (rc_lds == MDF_EUNSUPPORTED) {
       gx_used = gx;
+      mdf::note_wgrad_plan(1, 0, 1, 16, p.n_items, gx, gy, 3, p.split);
       hipLaunchKernelGGL(wgrad_kernel, dim3(gx, gy, 3), dim3(256), 0, (hipStream_t)stream, p);
     }
   }
@@ -691,6 +694,7 @@ static int conv2d_wgrad_impl(const float* small_, const float* big, float* dw, f
   }
   if (rc_lds == MDF_EUNSUPPORTED) {
     gx_used = gx;
+    mdf::note_wgrad_plan(4, 0, 1, 16, p.n_items, gx, gy, ksize, p.split);
     if (ksize == 1) hipLaunchKernelGGL(wgrad2d_kernel<1>, grid, dim3(256), 0, st, p);
     else if (ksize == 3) hipLaunchKernelGGL(wgrad2d_kernel<3>, grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL(wgrad2d_kernel<5>, grid, dim3(256), 0, st, p);

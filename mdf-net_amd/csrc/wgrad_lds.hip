@@ -458,6 +458,7 @@ int mdf_wgrad_lds_dispatch(const float* small_, const float* big, float* workspa
   *gx_io = gx;
   const dim3 grid(gx, gy, is3d ? 3 : ksize);
   hipStream_t st = (hipStream_t)stream;
+  mdf::note_wgrad_plan(0, R, TH, p.tv, p.n_tiles, gx, gy, (int)grid.z, p.split);      // (a shape without an instantiation falls back: the direct form overwrites it)
 #define WG_LAUNCH_TH(KHv, KWv, M3, Rv, THv)                                                                               \
   {                                                                                                                        \
     if (g_batching) {       /* recorded: launched by mdf_wgrad_batch_flush together with the other layers of this instantiation */ \
