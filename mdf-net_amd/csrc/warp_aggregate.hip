@@ -19,6 +19,9 @@
 //            blend, form the group similarities in registers, reduce the view-weight dot product
 //            across the pixel's lanes with wavefront shuffles, and accumulate over views.
 //
+// Both forms of phase A (fill_taps, FixedPairs), the hypothesis fetch, the four-tap gather with ATen's blend order and the
+// per-pixel soft-max are defined once, in warp_common.h, for these kernels and the training kernels alike.
+//
 // Compile with -ffp-contract=off: every fused multiply-add below is explicit.
 #include <cstdlib>
 #include "warp_common.h"
@@ -78,53 +81,13 @@ __global__ __launch_bounds__(kThreads) void warp_kernel(const Params p) {
   const size_t map_stride = (size_t)hw * C;
   const unsigned lane_b = 16u * (unsigned)sub;      // byte offset of this lane's 4 channels inside a texel
 
-  // phase A bookkeeping: when the (pixel, view) pairs of the tile divide the block (5 views: 4 x PPB = 256 / 128 / 64), a thread keeps
-  // ITS pair over all planes and chunks, so the pair's index arithmetic, its three 16-byte loads of the projection and rot_xyz are done
-  // once per kernel instead of once per sample (they were a third of the per-sample instructions; the kernel is VALU-bound)
-  const int npair = PPB * p.n_src;
-  const bool fixed_pair = (kThreads % npair) == 0;
-  const int pa_pair = tid % npair, pa_grp = tid / npair, pa_ngrp = kThreads / npair;
-  const int pa_pl = pa_pair % PPB, pa_v = pa_pair / PPB;
-  bool pa_live;
-  const int pa_pix = pt.pix(pa_pl, p.g.w, p.g.h, pa_live);
-  PixelRay ray{};
-  if (fixed_pair) {
-    const int yy = pa_pix / p.g.w, xx = pa_pix - yy * p.g.w;
-    ray = warp_ray(p.proj + ((size_t)pa_v * p.B + b) * 12, (float)xx, (float)yy);
-  }
+  const FixedPairs<1, PPB> fp(pt, p, b);
 
   for (int d0 = 0; d0 < p.D; d0 += p.dchunk) {
     const int nd = min(p.dchunk, p.D - d0);
     // ---------------- phase A: one thread per (plane, view, pixel) sample
-    if (fixed_pair) {
-      for (int ed = pa_grp; ed < nd; ed += pa_ngrp) {
-        const int d = d0 + ed;
-        const float dep = p.hypos_per_pixel ? p.hypos[((size_t)b * p.D + d) * hw + pa_pix] : p.hypos[(size_t)b * p.D + d];
-        float ix, iy;
-        warp_position_ray(ray, dep, p.g, ix, iy);
-        TapEntry t;
-        make_taps(ix, iy, p.g, C, t);
-        tab[(ed * p.n_src + pa_v) * PPB + pa_pl] = t;
-      }
-    } else {
-      const int nent = nd * p.n_src * PPB;
-      for (int e = tid; e < nent; e += kThreads) {
-        const int epl = e % PPB;
-        const int ev = (e / PPB) % p.n_src;
-        const int ed = e / (PPB * p.n_src);
-        bool elive;
-        const int epix = pt.pix(epl, p.g.w, p.g.h, elive);
-        const int yy = epix / p.g.w, xx = epix - yy * p.g.w;
-        const float* m = p.proj + ((size_t)ev * p.B + b) * 12;
-        const int d = d0 + ed;
-        const float dep = p.hypos_per_pixel ? p.hypos[((size_t)b * p.D + d) * hw + epix] : p.hypos[(size_t)b * p.D + d];
-        float ix, iy;
-        warp_position(m, (float)xx, (float)yy, dep, p.g, ix, iy);
-        TapEntry t;
-        make_taps(ix, iy, p.g, C, t);
-        tab[e] = t;
-      }
-    }
+    if (fp.active()) fp.fill(tab, p, b, d0, nd, C);
+    else fill_taps<PPB>(tab, pt, p, b, d0, nd, C);
     __syncthreads();
     // ---------------- phase B
     for (int dd = 0; dd < nd; ++dd) {
@@ -138,20 +101,9 @@ __global__ __launch_bounds__(kThreads) void warp_kernel(const Params p) {
       }
       for (int v = 0; v < p.n_src; ++v) {
         const TapEntry t = tab[(dd * p.n_src + v) * PPB + pl];
-        // uniform base (SGPR pair) + 32-bit byte offset per lane: `global_load_dwordx4 v, v_off, s[base]`.  With per-lane 64-bit
-        // pointers the four gathers cost 13 VALU instructions of address arithmetic per (plane, view) -- a fifth of this loop,
-        // which is VALU-bound (r03, ISA of warp_kernel<32,kVec>)
         const char* sb = reinterpret_cast<const char*>(p.src[v] + (size_t)b * map_stride);
-        const float4 nw = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[0] * 4u + lane_b));
-        const float4 ne = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[1] * 4u + lane_b));
-        const float4 sw = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[2] * 4u + lane_b));
-        const float4 se = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[3] * 4u + lane_b));
         float val[4];
-        // ATen tap order: nw*w + ne*w + sw*w + se*w, each step one fma
-        val[0] = __fmaf_rn(se.x, t.wt[3], __fmaf_rn(sw.x, t.wt[2], __fmaf_rn(ne.x, t.wt[1], __fmul_rn(nw.x, t.wt[0]))));
-        val[1] = __fmaf_rn(se.y, t.wt[3], __fmaf_rn(sw.y, t.wt[2], __fmaf_rn(ne.y, t.wt[1], __fmul_rn(nw.y, t.wt[0]))));
-        val[2] = __fmaf_rn(se.z, t.wt[3], __fmaf_rn(sw.z, t.wt[2], __fmaf_rn(ne.z, t.wt[1], __fmul_rn(nw.z, t.wt[0]))));
-        val[3] = __fmaf_rn(se.w, t.wt[3], __fmaf_rn(sw.w, t.wt[2], __fmaf_rn(ne.w, t.wt[1], __fmul_rn(nw.w, t.wt[0]))));
+        gather_blend(sb, t, lane_b, val);
         if (MODE == kWarp) {
 #pragma unroll
           for (int k = 0; k < 4; ++k) acc[k] = val[k];
@@ -165,16 +117,12 @@ __global__ __launch_bounds__(kThreads) void warp_kernel(const Params p) {
           acc[0] += wv * sim0;
           acc[1] += wv * sim1;
         } else {  // kVar: softmax over all C channels of this pixel (homoaggregate.py:60)
-          const float mx = pixel_max<LPP>(fmaxf(fmaxf(val[0], val[1]), fmaxf(val[2], val[3])));
-          float e[4];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) e[k] = expf(val[k] - mx);
-          const float den = pixel_sum<LPP>((e[0] + e[1]) + (e[2] + e[3]));
+          float pr[4];
+          softmax_pixel<LPP>(val, pr);
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            const float pr = e[k] / den;
-            acc[k] += pr;
-            acc2[k] += pr * pr;
+            acc[k] += pr[k];
+            acc2[k] += pr[k] * pr[k];
           }
         }
       }
@@ -262,58 +210,12 @@ __global__ __launch_bounds__(kThreads, MDF_VEC8_MIN_BLOCKS) void warp_vec8_kerne
   const size_t map_stride = (size_t)hw * C;
   const unsigned lane_b = 32u * (unsigned)sub;      // byte offset of this lane's 8 channels inside a texel
 
-  // tap table: a thread keeps its (pixel, view) pair(s) over the planes (warp_kernel, phase A); here a tile has up to 2 pairs per thread
-  const int npair = PPB * p.n_src;
-  const bool few = (npair <= kThreads) && (kThreads % npair) == 0;          // >= 1 thread group per pair set
-  const bool two = (npair == 2 * kThreads);                                 // exactly two pairs per thread
-  const int pa_ngrp = few ? kThreads / npair : 1, pa_grp = few ? tid / npair : 0;
-  PixelRay ray[2];
-  int pa_pl[2], pa_v[2], pa_pix[2];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int pair = (few ? tid % npair : tid) + k * kThreads;
-    pa_pl[k] = pair % PPB; pa_v[k] = min(pair / PPB, p.n_src - 1);
-    bool pa_live;
-    pa_pix[k] = pt.pix(pa_pl[k], p.g.w, p.g.h, pa_live);
-    const int yy = pa_pix[k] / p.g.w, xx = pa_pix[k] - yy * p.g.w;
-    ray[k] = warp_ray(p.proj + ((size_t)pa_v[k] * p.B + b) * 12, (float)xx, (float)yy);
-  }
+  const FixedPairs<2, PPB> fp(pt, p, b);      // here a tile has up to 2 (pixel, view) pairs per thread
 
   for (int d0 = 0; d0 < p.D; d0 += p.dchunk) {
     const int nd = min(p.dchunk, p.D - d0);
-    if (few || two) {
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        if (k == 1 && !two) break;
-        for (int ed = pa_grp; ed < nd; ed += pa_ngrp) {
-          const int d = d0 + ed;
-          const float dep = p.hypos_per_pixel ? p.hypos[((size_t)b * p.D + d) * hw + pa_pix[k]] : p.hypos[(size_t)b * p.D + d];
-          float ix, iy;
-          warp_position_ray(ray[k], dep, p.g, ix, iy);
-          TapEntry t;
-          make_taps(ix, iy, p.g, C, t);
-          tab[(ed * p.n_src + pa_v[k]) * PPB + pa_pl[k]] = t;
-        }
-      }
-    } else {
-      const int nent = nd * p.n_src * PPB;
-      for (int e = tid; e < nent; e += kThreads) {
-        const int epl = e % PPB;
-        const int ev = (e / PPB) % p.n_src;
-        const int ed = e / (PPB * p.n_src);
-        bool elive;
-        const int epix = pt.pix(epl, p.g.w, p.g.h, elive);
-        const int yy = epix / p.g.w, xx = epix - yy * p.g.w;
-        const float* m = p.proj + ((size_t)ev * p.B + b) * 12;
-        const int d = d0 + ed;
-        const float dep = p.hypos_per_pixel ? p.hypos[((size_t)b * p.D + d) * hw + epix] : p.hypos[(size_t)b * p.D + d];
-        float ix, iy;
-        warp_position(m, (float)xx, (float)yy, dep, p.g, ix, iy);
-        TapEntry t;
-        make_taps(ix, iy, p.g, C, t);
-        tab[e] = t;
-      }
-    }
+    if (fp.active()) fp.fill(tab, p, b, d0, nd, C);
+    else fill_taps<PPB>(tab, pt, p, b, d0, nd, C);
     __syncthreads();
     for (int dd = 0; dd < nd; ++dd) {
       float acc[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
@@ -324,17 +226,10 @@ __global__ __launch_bounds__(kThreads, MDF_VEC8_MIN_BLOCKS) void warp_vec8_kerne
         float sim[2][2], part[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          const unsigned lb = lane_b + 16u * j;
-          const float4 nw = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[0] * 4u + lb));
-          const float4 ne = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[1] * 4u + lb));
-          const float4 sw = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[2] * 4u + lb));
-          const float4 se = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[3] * 4u + lb));
-          const float v0 = __fmaf_rn(se.x, t.wt[3], __fmaf_rn(sw.x, t.wt[2], __fmaf_rn(ne.x, t.wt[1], __fmul_rn(nw.x, t.wt[0]))));
-          const float v1 = __fmaf_rn(se.y, t.wt[3], __fmaf_rn(sw.y, t.wt[2], __fmaf_rn(ne.y, t.wt[1], __fmul_rn(nw.y, t.wt[0]))));
-          const float v2 = __fmaf_rn(se.z, t.wt[3], __fmaf_rn(sw.z, t.wt[2], __fmaf_rn(ne.z, t.wt[1], __fmul_rn(nw.z, t.wt[0]))));
-          const float v3 = __fmaf_rn(se.w, t.wt[3], __fmaf_rn(sw.w, t.wt[2], __fmaf_rn(ne.w, t.wt[1], __fmul_rn(nw.w, t.wt[0]))));
-          sim[j][0] = __fmaf_rn(softmax2_p0(v0, v1), rd[j][0], r1[j][0]);   // homoaggregate.py:38-39
-          sim[j][1] = __fmaf_rn(softmax2_p0(v2, v3), rd[j][1], r1[j][1]);
+          float val[4];
+          gather_blend(sb, t, lane_b + 16u * j, val);
+          sim[j][0] = __fmaf_rn(softmax2_p0(val[0], val[1]), rd[j][0], r1[j][0]);   // homoaggregate.py:38-39
+          sim[j][1] = __fmaf_rn(softmax2_p0(val[2], val[3]), rd[j][1], r1[j][1]);
           part[j] = __fmaf_rn(cw[j][0], sim[j][0], cw[j][1] * sim[j][1]);
         }
         const float z = pixel_sum<LPP>(part[0] + part[1]);                     // Conv3d(G->1, 1x1x1); first tree step in the lane
@@ -390,8 +285,8 @@ int launch_vec8(Params& p, hipStream_t st) {
 // every sum are warp_vec8_kernel's / warp_kernel<16,kVec>'s, so with d computed exactly the only difference is the rounding of
 // the blend (one blend of a difference instead of the difference of two blends).
 // GPL = groups per lane (4 or 8): G / GPL lanes per pixel; at G = GPL a pixel is one lane and needs no cross-lane step.
-// FIXED: the tile's (pixel, view) pairs are one or two per thread, kept over the planes (warp_vec8_kernel's `few` / `two`, decided by
-// the launcher); else the generic tap-table loop.  Two instantiations instead of a branch: with both paths in one kernel the register
+// FIXED: the tile's (pixel, view) pairs are one or two per thread, kept over the planes (FixedPairs<2>, decided by the launcher);
+// else the generic tap-table loop.  Two instantiations instead of a branch: with both paths in one kernel the register
 // allocation is the generic path's (133 registers at GPL = 8, three waves per SIMD, instead of 96 and five).
 template <int G, int GPL, bool FIXED>
 __global__ __launch_bounds__(kThreads) void warp_pairdiff_kernel(const Params p) {
@@ -426,61 +321,12 @@ __global__ __launch_bounds__(kThreads) void warp_pairdiff_kernel(const Params p)
   const float alpha = p.wpar[G], beta = p.wpar[G + 1], w2 = p.wpar[G + 2], b2 = p.wpar[G + 3];
   const size_t map_stride = (size_t)hw * G;
   const unsigned lane_b = 4u * GPL * (unsigned)sub;   // byte offset of this lane's groups inside a texel
-
-  // tap table: as warp_vec8_kernel (a thread keeps up to two (pixel, view) pairs over the planes)
-  const int npair = PPB * p.n_src;
-  const bool few = (npair <= kThreads) && (kThreads % npair) == 0;
-  const bool two = (npair == 2 * kThreads);
-  const int pa_ngrp = few ? kThreads / npair : 1, pa_grp = few ? tid / npair : 0;
-  PixelRay ray[2];
-  int pa_pl[2], pa_v[2], pa_pix[2];
-  if constexpr (FIXED) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int pair = (few ? tid % npair : tid) + k * kThreads;
-      pa_pl[k] = pair % PPB; pa_v[k] = min(pair / PPB, p.n_src - 1);
-      bool pa_live;
-      pa_pix[k] = pt.pix(pa_pl[k], p.g.w, p.g.h, pa_live);
-      const int yy = pa_pix[k] / p.g.w, xx = pa_pix[k] - yy * p.g.w;
-      ray[k] = warp_ray(p.proj + ((size_t)pa_v[k] * p.B + b) * 12, (float)xx, (float)yy);
-    }
-  }
+  const FixedPairs<2, PPB> fp(pt, p, b, FIXED);
 
   for (int d0 = 0; d0 < p.D; d0 += p.dchunk) {
     const int nd = min(p.dchunk, p.D - d0);
-    if constexpr (FIXED) {
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        if (k == 1 && !two) break;
-        for (int ed = pa_grp; ed < nd; ed += pa_ngrp) {
-          const int d = d0 + ed;
-          const float dep = p.hypos_per_pixel ? p.hypos[((size_t)b * p.D + d) * hw + pa_pix[k]] : p.hypos[(size_t)b * p.D + d];
-          float ix, iy;
-          warp_position_ray(ray[k], dep, p.g, ix, iy);
-          TapEntry t;
-          make_taps(ix, iy, p.g, G, t);
-          tab[(ed * p.n_src + pa_v[k]) * PPB + pa_pl[k]] = t;
-        }
-      }
-    } else {
-      const int nent = nd * p.n_src * PPB;
-      for (int e = tid; e < nent; e += kThreads) {
-        const int epl = e % PPB;
-        const int ev = (e / PPB) % p.n_src;
-        const int ed = e / (PPB * p.n_src);
-        bool elive;
-        const int epix = pt.pix(epl, p.g.w, p.g.h, elive);
-        const int yy = epix / p.g.w, xx = epix - yy * p.g.w;
-        const float* m = p.proj + ((size_t)ev * p.B + b) * 12;
-        const int d = d0 + ed;
-        const float dep = p.hypos_per_pixel ? p.hypos[((size_t)b * p.D + d) * hw + epix] : p.hypos[(size_t)b * p.D + d];
-        float ix, iy;
-        warp_position(m, (float)xx, (float)yy, dep, p.g, ix, iy);
-        TapEntry t;
-        make_taps(ix, iy, p.g, G, t);
-        tab[e] = t;
-      }
-    }
+    if constexpr (FIXED) fp.fill(tab, p, b, d0, nd, G);
+    else fill_taps<PPB>(tab, pt, p, b, d0, nd, G);
     __syncthreads();
     for (int dd = 0; dd < nd; ++dd) {
       float acc[GPL];
@@ -494,16 +340,8 @@ __global__ __launch_bounds__(kThreads) void warp_pairdiff_kernel(const Params p)
         float part = 0.f;
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {
-          const unsigned lb = lane_b + 16u * j;
-          const float4 nw = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[0] * 4u + lb));
-          const float4 ne = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[1] * 4u + lb));
-          const float4 sw = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[2] * 4u + lb));
-          const float4 se = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[3] * 4u + lb));
-          float dv[4];   // ATen tap order: nw*w + ne*w + sw*w + se*w, each step one fma
-          dv[0] = __fmaf_rn(se.x, t.wt[3], __fmaf_rn(sw.x, t.wt[2], __fmaf_rn(ne.x, t.wt[1], __fmul_rn(nw.x, t.wt[0]))));
-          dv[1] = __fmaf_rn(se.y, t.wt[3], __fmaf_rn(sw.y, t.wt[2], __fmaf_rn(ne.y, t.wt[1], __fmul_rn(nw.y, t.wt[0]))));
-          dv[2] = __fmaf_rn(se.z, t.wt[3], __fmaf_rn(sw.z, t.wt[2], __fmaf_rn(ne.z, t.wt[1], __fmul_rn(nw.z, t.wt[0]))));
-          dv[3] = __fmaf_rn(se.w, t.wt[3], __fmaf_rn(sw.w, t.wt[2], __fmaf_rn(ne.w, t.wt[1], __fmul_rn(nw.w, t.wt[0]))));
+          float dv[4];   // the blend of 4 pair differences: a texel here is G floats, the tap offsets are in floats all the same
+          gather_blend(sb, t, lane_b + 16u * j, dv);
           float q[2];    // the partial dot product of a 4-channel slice of the full-feature kernels (two groups)
 #pragma unroll
           for (int h2 = 0; h2 < 2; ++h2) {
@@ -552,8 +390,7 @@ int launch_pairdiff(Params& p, hipStream_t st) {
   p.dchunk = dch;
   const size_t lds = (size_t)dch * p.n_src * ppb * sizeof(TapEntry);
   if (lds > 64 * 1024) return MDF_EUNSUPPORTED;
-  const int npair = ppb * p.n_src;
-  if ((npair <= kThreads && kThreads % npair == 0) || npair == 2 * kThreads)
+  if (FixedPairs<2, ppb>::usable(p.n_src))
     hipLaunchKernelGGL((warp_pairdiff_kernel<G, GPL, true>), dim3(p.nblk_x, p.B), dim3(kThreads), lds, st, p);
   else
     hipLaunchKernelGGL((warp_pairdiff_kernel<G, GPL, false>), dim3(p.nblk_x, p.B), dim3(kThreads), lds, st, p);
@@ -587,12 +424,11 @@ __global__ __launch_bounds__(kThreads) void warp_vec_win_kernel(const Params p, 
   const int hw = p.g.h * p.g.w;
   const int W = p.g.w;
   const int b = blockIdx.y;
-  const int tile = (int)mdf::xcd_remap(blockIdx.x, p.nblk_x);
-  const int pix0 = tile * PPB;
+  const PixTile<PPB, 0> pt((int)mdf::xcd_remap(blockIdx.x, p.nblk_x), W);   // a run of a row
   const int tid = threadIdx.x;
   const int pl = tid / LPP, sub = tid % LPP;
-  const int pix = min(pix0 + pl, hw - 1);
-  const bool live = (pix0 + pl) < hw;
+  bool live;
+  const int pix = pt.pix(pl, W, p.g.h, live);
 
   float r[4];
   {
@@ -610,27 +446,13 @@ __global__ __launch_bounds__(kThreads) void warp_vec_win_kernel(const Params p, 
     const int nd = min(p.dchunk, p.D - d0);
     if (tid < 4 * p.n_src) bb[tid >> 2][tid & 3] = (tid & 1) ? INT32_MIN : INT32_MAX;
     __syncthreads();
-    const int nent = nd * p.n_src * PPB;
-    for (int e = tid; e < nent; e += kThreads) {
-      const int epl = e % PPB;
-      const int ev = (e / PPB) % p.n_src;
-      const int ed = e / (PPB * p.n_src);
-      const int epix = min(pix0 + epl, hw - 1);
-      const int yy = epix / W, xx = epix - yy * W;
-      const float* m = p.proj + ((size_t)ev * p.B + b) * 12;
-      const int d = d0 + ed;
-      const float dep = p.hypos_per_pixel ? p.hypos[((size_t)b * p.D + d) * hw + epix] : p.hypos[(size_t)b * p.D + d];
-      float ix, iy;
-      warp_position(m, (float)xx, (float)yy, dep, p.g, ix, iy);
-      TapXY t;
-      tap_weights_corners(ix, iy, p.g, t.wt, t.xa, t.xb, t.ya, t.yb);
-      tab[e] = t;
+    fill_taps<PPB>(tab, pt, p, b, d0, nd, 0, p.n_src, C, [&](int ev, bool, const TapXY& t) {
       // every tap is READ (a zero weight still multiplies a finite value), so the box covers all four clamped corners
       atomicMin(&bb[ev][0], t.xa);
       atomicMax(&bb[ev][1], t.xb);
       atomicMin(&bb[ev][2], t.ya);
       atomicMax(&bb[ev][3], t.yb);
-    }
+    });
     __syncthreads();
     if (tid == 0) {   // hand out pool space view by view
       int used = 0;
@@ -678,12 +500,10 @@ __global__ __launch_bounds__(kThreads) void warp_vec_win_kernel(const Params p, 
           sw = *reinterpret_cast<const float4*>(sp + (size_t)(t.yb * W + t.xa) * C);
           se = *reinterpret_cast<const float4*>(sp + (size_t)(t.yb * W + t.xb) * C);
         }
-        const float v0 = __fmaf_rn(se.x, t.wt[3], __fmaf_rn(sw.x, t.wt[2], __fmaf_rn(ne.x, t.wt[1], __fmul_rn(nw.x, t.wt[0]))));
-        const float v1 = __fmaf_rn(se.y, t.wt[3], __fmaf_rn(sw.y, t.wt[2], __fmaf_rn(ne.y, t.wt[1], __fmul_rn(nw.y, t.wt[0]))));
-        const float v2 = __fmaf_rn(se.z, t.wt[3], __fmaf_rn(sw.z, t.wt[2], __fmaf_rn(ne.z, t.wt[1], __fmul_rn(nw.z, t.wt[0]))));
-        const float v3 = __fmaf_rn(se.w, t.wt[3], __fmaf_rn(sw.w, t.wt[2], __fmaf_rn(ne.w, t.wt[1], __fmul_rn(nw.w, t.wt[0]))));
-        const float sim0 = __fmaf_rn(softmax2_p0(v0, v1), r[0], r[1]);
-        const float sim1 = __fmaf_rn(softmax2_p0(v2, v3), r[2], r[3]);
+        float val[4];
+        blend_taps(nw, ne, sw, se, t.wt, val);     // (its own addresses: an LDS window, or 64-bit global pointers)
+        const float sim0 = __fmaf_rn(softmax2_p0(val[0], val[1]), r[0], r[1]);
+        const float sim1 = __fmaf_rn(softmax2_p0(val[2], val[3]), r[2], r[3]);
         const float z = pixel_sum<LPP>(__fmaf_rn(cw0, sim0, cw1 * sim1));
         const float u = __fmaf_rn(fmaxf(__fmaf_rn(z, alpha, beta), 0.0f), w2, b2);
         const float wv = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-u * kLog2e));
@@ -777,16 +597,18 @@ int launch(Params& p, int C, hipStream_t st) {
   return mdf::check_launch("warp_kernel");
 }
 
+int check_layout(int fea_layout) {
+  if (fea_layout != MDF_FEA_NHWC)
+    return mdf::fail(MDF_EUNSUPPORTED, "feature layout %d not supported (kernels gather NHWC taps)", fea_layout);
+  return MDF_OK;
+}
+
 int check_common(const void* a, const void* b, const void* c, const void* d, int fea_layout, int B, int C, int D, int h,
                  int w) {
   MDF_REQUIRE(a && b && c && d, "null pointer argument");
-  MDF_REQUIRE(B > 0 && D > 0 && h > 1 && w > 1, "bad shape B=%d D=%d h=%d w=%d", B, D, h, w);
-  MDF_REQUIRE((long long)h * w * C < (1ll << 30), "feature map too large for 32-bit byte offsets");
-  if (fea_layout != MDF_FEA_NHWC)
-    return mdf::fail(MDF_EUNSUPPORTED, "feature layout %d not supported (kernels gather NHWC taps)", fea_layout);
-  if (C != 16 && C != 32 && C != 64)
-    return mdf::fail(MDF_EUNSUPPORTED, "C=%d not supported (built for 16, 32, 64)", C);
-  return MDF_OK;
+  if (int rc = check_shape(B, D, h, w, C)) return rc;
+  if (int rc = check_layout(fea_layout)) return rc;
+  return check_channels(C);
 }
 
 }  // namespace
@@ -822,14 +644,11 @@ extern "C" int mdf_warp_aggregate_vec_fwd(const float* ref_fea, const float* con
                                           int D, int h, int w, int n_src, void* stream) {
   if (int rc = check_common(ref_fea, proj, hypos, cost, fea_layout, B, C, D, h, w)) return rc;
   MDF_REQUIRE(src_feas && w_params, "null pointer argument");
-  MDF_REQUIRE(n_src >= 1 && n_src <= MDF_MAX_SRC_VIEWS, "n_src=%d out of range [1,%d]", n_src, MDF_MAX_SRC_VIEWS);
+  if (int rc = check_n_src(n_src)) return rc;
   if (G * 2 != C) return mdf::fail(MDF_EUNSUPPORTED, "only C/G == 2 is built (C=%d, G=%d)", C, G);
   Params p{};
   p.ref = ref_fea;
-  for (int v = 0; v < n_src; ++v) {
-    MDF_REQUIRE(src_feas[v], "src_feas[%d] is null", v);
-    p.src[v] = src_feas[v];
-  }
+  if (int rc = copy_views(p.src, src_feas, n_src, "src_feas")) return rc;
   p.proj = proj; p.hypos = hypos; p.wpar = w_params; p.out = cost;
   p.g = make_geom(h, w);
   p.B = B; p.D = D; p.n_src = n_src; p.hypos_per_pixel = hypos_per_pixel; p.out_ndhwc = (cost_layout == MDF_VOL_NDHWC);
@@ -862,19 +681,14 @@ extern "C" int mdf_warp_aggregate_pairdiff_fwd(const float* ref_diff, const floa
                                                const float* w_params, float* cost, int cost_layout, int B, int G, int D,
                                                int h, int w, int n_src, void* stream) {
   MDF_REQUIRE(ref_diff && src_diffs && proj && hypos && w_params && cost, "null pointer argument");
-  MDF_REQUIRE(B > 0 && D > 0 && h > 1 && w > 1, "bad shape B=%d D=%d h=%d w=%d", B, D, h, w);
-  MDF_REQUIRE((long long)h * w * G < (1ll << 30), "feature map too large for 32-bit byte offsets");
-  MDF_REQUIRE(n_src >= 1 && n_src <= MDF_MAX_SRC_VIEWS, "n_src=%d out of range [1,%d]", n_src, MDF_MAX_SRC_VIEWS);
-  if (fea_layout != MDF_FEA_NHWC)
-    return mdf::fail(MDF_EUNSUPPORTED, "feature layout %d not supported (kernels gather NHWC taps)", fea_layout);
+  if (int rc = check_shape(B, D, h, w, G)) return rc;
+  if (int rc = check_n_src(n_src)) return rc;
+  if (int rc = check_layout(fea_layout)) return rc;
   if (G != 8 && G != 16 && G != 32)
     return mdf::fail(MDF_EUNSUPPORTED, "G=%d not supported (pair-difference maps are built for 8, 16, 32 groups)", G);
   Params p{};
   p.ref = ref_diff;
-  for (int v = 0; v < n_src; ++v) {
-    MDF_REQUIRE(src_diffs[v], "src_diffs[%d] is null", v);
-    p.src[v] = src_diffs[v];
-  }
+  if (int rc = copy_views(p.src, src_diffs, n_src, "src_diffs")) return rc;
   p.proj = proj; p.hypos = hypos; p.wpar = w_params; p.out = cost;
   p.g = make_geom(h, w);
   p.B = B; p.D = D; p.n_src = n_src; p.hypos_per_pixel = hypos_per_pixel; p.out_ndhwc = (cost_layout == MDF_VOL_NDHWC);
@@ -902,13 +716,10 @@ extern "C" int mdf_warp_aggregate_var_fwd(const float* ref_fea, const float* con
                                           int cost_layout, int B, int C, int D, int h, int w, int n_src, void* stream) {
   if (int rc = check_common(ref_fea, proj, hypos, cost, fea_layout, B, C, D, h, w)) return rc;
   MDF_REQUIRE(src_feas, "null pointer argument");
-  MDF_REQUIRE(n_src >= 1 && n_src <= MDF_MAX_SRC_VIEWS, "n_src=%d out of range [1,%d]", n_src, MDF_MAX_SRC_VIEWS);
+  if (int rc = check_n_src(n_src)) return rc;
   Params p{};
   p.ref = ref_fea;
-  for (int v = 0; v < n_src; ++v) {
-    MDF_REQUIRE(src_feas[v], "src_feas[%d] is null", v);
-    p.src[v] = src_feas[v];
-  }
+  if (int rc = copy_views(p.src, src_feas, n_src, "src_feas")) return rc;
   p.proj = proj; p.hypos = hypos; p.out = cost;
   p.g = make_geom(h, w);
   p.B = B; p.D = D; p.n_src = n_src; p.hypos_per_pixel = hypos_per_pixel; p.out_ndhwc = (cost_layout == MDF_VOL_NDHWC);

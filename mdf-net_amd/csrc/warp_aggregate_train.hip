@@ -9,13 +9,14 @@
 //   kFwd        cost = sum_v w_v sim_v / sum_v w_v with per-view (alpha_v, beta_v); also writes wsum = sum_v w_v
 //   kBwdReduce  per view S1 = sum dz, S2 = sum dz*xhat (BatchNorm backward), plus d w2, d b2   (fp64 atomics)
 //   kBwd        dt -> dsim -> d ref (direct store: a block owns its pixels over all planes), d src (scatter through the
-//               4 bilinear taps -- the transpose of the gather -- staged in an LDS window, see warp_bwd_kernel), d conv weight
+//               4 bilinear taps -- the transpose of the gather -- staged in an LDS window, warp_scatter.h), d conv weight
 // Same thread mapping as the eval kernel (warp_aggregate.hip): a lane owns 4 channels = 2 groups, the C/4 lanes of a
-// pixel reduce with DPP row operations, sample positions are computed once per (pixel, plane, view) into an LDS table.
+// pixel reduce with DPP row operations, sample positions are computed once per (pixel, plane, view) into an LDS table
+// (phase A, gather and blend: warp_common.h).
 //
 // par (float):  [0,G) conv weight | G: w2, G+1: b2, G+2: gamma, G+3: 1/N | G+4+4v..: alpha_v, beta_v, mean_v, invstd_v
 #include <cstdlib>
-#include "warp_common.h"
+#include "warp_scatter.h"
 
 namespace {
 
@@ -60,13 +61,12 @@ __global__ __launch_bounds__(kThreads) void warp_train_kernel(const TrainParams 
 
   const int hw = p.g.h * p.g.w;
   const int b = blockIdx.y;
-  const int tile = (int)mdf::xcd_remap(blockIdx.x, p.nblk_x);
-  const int pix0 = tile * PPB;
+  const PixTile<PPB, 0> pt((int)mdf::xcd_remap(blockIdx.x, p.nblk_x), p.g.w);   // a run of a row
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int pl = tid / LPP, sub = tid % LPP;
-  const int pix = min(pix0 + pl, hw - 1);
-  const bool live = (pix0 + pl) < hw;
+  bool live;
+  const int pix = pt.pix(pl, p.g.w, p.g.h, live);
   const bool owner = live && (sub == 0);   // one lane per pixel contributes pixel-level scalars to the reductions
 
   // reference features: group softmax
@@ -86,49 +86,13 @@ __global__ __launch_bounds__(kThreads) void warp_train_kernel(const TrainParams 
   const int nred = (PASS == kStats) ? 2 * p.n_src : 2 * p.n_src + 2;
   double total = 0.0;                 // thread k < nred: block total of reduction slot k
 
-  // tap table: a thread keeps its (pixel, view) pair over the planes when the pairs divide the block (warp_aggregate.hip, phase A)
-  const int npair = PPB * p.n_src;
-  const bool fixed_pair = (kThreads % npair) == 0;
-  const int pa_pair = tid % npair, pa_grp = tid / npair, pa_ngrp = kThreads / npair;
-  const int pa_pl = pa_pair % PPB, pa_v = pa_pair / PPB;
-  const int pa_pix = min(pix0 + pa_pl, hw - 1);
-  PixelRay ray{};
-  if (fixed_pair) {
-    const int yy = pa_pix / p.g.w, xx = pa_pix - yy * p.g.w;
-    ray = warp_ray(p.proj + ((size_t)pa_v * p.B + b) * 12, (float)xx, (float)yy);
-  }
+  const FixedPairs<1, PPB> fp(pt, p, b);
 
   const int dlo = blockIdx.z * p.dslice, dhi = min(p.D, dlo + p.dslice);
   for (int d0 = dlo; d0 < dhi; d0 += p.dchunk) {
     const int nd = min(p.dchunk, dhi - d0);
-    if (fixed_pair) {
-      for (int ed = pa_grp; ed < nd; ed += pa_ngrp) {
-        const int d = d0 + ed;
-        const float dep = p.hypos_per_pixel ? p.hypos[((size_t)b * p.D + d) * hw + pa_pix] : p.hypos[(size_t)b * p.D + d];
-        float ix, iy;
-        warp_position_ray(ray, dep, p.g, ix, iy);
-        TapEntry t;
-        make_taps(ix, iy, p.g, C, t);
-        tab[(ed * p.n_src + pa_v) * PPB + pa_pl] = t;
-      }
-    } else {
-      const int nent = nd * p.n_src * PPB;
-      for (int e = tid; e < nent; e += kThreads) {
-        const int epl = e % PPB;
-        const int ev = (e / PPB) % p.n_src;
-        const int ed = e / (PPB * p.n_src);
-        const int epix = min(pix0 + epl, hw - 1);
-        const int yy = epix / p.g.w, xx = epix - yy * p.g.w;
-        const float* m = p.proj + ((size_t)ev * p.B + b) * 12;
-        const int d = d0 + ed;
-        const float dep = p.hypos_per_pixel ? p.hypos[((size_t)b * p.D + d) * hw + epix] : p.hypos[(size_t)b * p.D + d];
-        float ix, iy;
-        warp_position(m, (float)xx, (float)yy, dep, p.g, ix, iy);
-        TapEntry t;
-        make_taps(ix, iy, p.g, C, t);
-        tab[e] = t;
-      }
-    }
+    if (fp.active()) fp.fill(tab, p, b, d0, nd, C);
+    else fill_taps<PPB>(tab, pt, p, b, d0, nd, C);
     __syncthreads();
 
     if (PASS == kStats || PASS == kBwdReduce) {
@@ -136,19 +100,13 @@ __global__ __launch_bounds__(kThreads) void warp_train_kernel(const TrainParams 
       float a3 = 0.f, a4 = 0.f;
       for (int v = 0; v < p.n_src; ++v) {
         float s1 = 0.f, s2 = 0.f;
-        const char* sb = reinterpret_cast<const char*>(p.src[v] + (size_t)b * map_stride);     // uniform base + 32-bit lane offsets
+        const char* sb = reinterpret_cast<const char*>(p.src[v] + (size_t)b * map_stride);
         for (int dd = 0; dd < nd; ++dd) {
           const TapEntry t = tab[(dd * p.n_src + v) * PPB + pl];
-          const float4 nw = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[0] * 4u + lane_b));
-          const float4 ne = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[1] * 4u + lane_b));
-          const float4 sw = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[2] * 4u + lane_b));
-          const float4 se = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[3] * 4u + lane_b));
-          const float v0 = __fmaf_rn(se.x, t.wt[3], __fmaf_rn(sw.x, t.wt[2], __fmaf_rn(ne.x, t.wt[1], __fmul_rn(nw.x, t.wt[0]))));
-          const float v1 = __fmaf_rn(se.y, t.wt[3], __fmaf_rn(sw.y, t.wt[2], __fmaf_rn(ne.y, t.wt[1], __fmul_rn(nw.y, t.wt[0]))));
-          const float v2 = __fmaf_rn(se.z, t.wt[3], __fmaf_rn(sw.z, t.wt[2], __fmaf_rn(ne.z, t.wt[1], __fmul_rn(nw.z, t.wt[0]))));
-          const float v3 = __fmaf_rn(se.w, t.wt[3], __fmaf_rn(sw.w, t.wt[2], __fmaf_rn(ne.w, t.wt[1], __fmul_rn(nw.w, t.wt[0]))));
-          const float sim0 = __fmaf_rn(softmax2_p0(v0, v1), r[0], r[1]);
-          const float sim1 = __fmaf_rn(softmax2_p0(v2, v3), r[2], r[3]);
+          float val[4];
+          gather_blend(sb, t, lane_b, val);
+          const float sim0 = __fmaf_rn(softmax2_p0(val[0], val[1]), r[0], r[1]);
+          const float sim1 = __fmaf_rn(softmax2_p0(val[2], val[3]), r[2], r[3]);
           const float tt = pixel_sum<LPP>(__fmaf_rn(cw0, sim0, cw1 * sim1));
           if (PASS == kStats) {
             if (owner) { s1 += tt; s2 = fmaf(tt, tt, s2); }
@@ -190,15 +148,9 @@ __global__ __launch_bounds__(kThreads) void warp_train_kernel(const TrainParams 
         for (int v = 0; v < p.n_src; ++v) {
           const TapEntry t = tab[(dd * p.n_src + v) * PPB + pl];
           const char* sb = reinterpret_cast<const char*>(p.src[v] + (size_t)b * map_stride);
-          const float4 nw = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[0] * 4u + lane_b));
-          const float4 ne = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[1] * 4u + lane_b));
-          const float4 sw = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[2] * 4u + lane_b));
-          const float4 se = *reinterpret_cast<const float4*>(sb + ((unsigned)t.off[3] * 4u + lane_b));
-          const float v0 = __fmaf_rn(se.x, t.wt[3], __fmaf_rn(sw.x, t.wt[2], __fmaf_rn(ne.x, t.wt[1], __fmul_rn(nw.x, t.wt[0]))));
-          const float v1 = __fmaf_rn(se.y, t.wt[3], __fmaf_rn(sw.y, t.wt[2], __fmaf_rn(ne.y, t.wt[1], __fmul_rn(nw.y, t.wt[0]))));
-          const float v2 = __fmaf_rn(se.z, t.wt[3], __fmaf_rn(sw.z, t.wt[2], __fmaf_rn(ne.z, t.wt[1], __fmul_rn(nw.z, t.wt[0]))));
-          const float v3 = __fmaf_rn(se.w, t.wt[3], __fmaf_rn(sw.w, t.wt[2], __fmaf_rn(ne.w, t.wt[1], __fmul_rn(nw.w, t.wt[0]))));
-          const float q0 = softmax2_p0(v0, v1), q1 = softmax2_p0(v2, v3);
+          float val[4];
+          gather_blend(sb, t, lane_b, val);
+          const float q0 = softmax2_p0(val[0], val[1]), q1 = softmax2_p0(val[2], val[3]);
           const float sim0 = __fmaf_rn(q0, r[0], r[1]);
           const float sim1 = __fmaf_rn(q1, r[2], r[3]);
           const float tt = pixel_sum<LPP>(__fmaf_rn(cw0, sim0, cw1 * sim1));          // Conv3d(G->1, 1x1x1)
@@ -227,23 +179,10 @@ __global__ __launch_bounds__(kThreads) void warp_train_kernel(const TrainParams 
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// kBwd: the scatter.  The source-feature gradient of a softmax PAIR is antisymmetric (d v1 = -d v0), so only the even
-// channel of every group is accumulated ([B,h,w,G] buffers; the caller expands to (g, -g)).  Per (depth chunk, view)
-// the block finds the bounding box of its live taps in the source map; when it fits the LDS window the taps are
-// accumulated there with LDS atomics and the window is flushed once with DENSE global atomics (whole rows of the
-// window are contiguous in the NHWC gradient map) -- each texel is sent to memory once per chunk instead of once per
-// tap; a block whose footprint does not fit (strong rotation, very wide depth range) scatters to memory directly.
-#ifndef MDF_BWD_WIN_FLOATS
-#define MDF_BWD_WIN_FLOATS 4096
-#endif
-constexpr int kWinFloats = MDF_BWD_WIN_FLOATS;   // 16 KiB: with the tap table (16-32 KiB) four blocks per CU
-
-// LDS float add through an address-space-3 pointer: `ds_add_f32` (with a generic pointer next to the global fallback the
-// compiler merges both branches into one `flat_atomic_add_f32` on a selected 64-bit address).
-__device__ __forceinline__ void lds_add(float* p, float v) {
-  (void)__hip_atomic_fetch_add((__attribute__((address_space(3))) float*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
+// kBwd: the scatter (tile, tap table with bounding boxes, LDS window and its flush: warp_scatter.h).  The source-feature
+// gradient of a softmax PAIR is antisymmetric (d v1 = -d v0), so only the even channel of every group is accumulated
+// ([B,h,w,G] buffers, a window texel is G floats; the caller expands to (g, -g)).
+//
 // Thread mapping of the scatter: the four waves of a block split the CHANNELS of the tile's pixels (wave w owns channels
 // [w*C/4, (w+1)*C/4) of all PPB pixels), so two waves never touch the same (texel, channel) of the window, and a lane needs
 // nothing from the other channels of its pixel: the per-sample scalars (view weight, dz, t) come from pass 2 (`aux`).
@@ -254,21 +193,15 @@ __device__ __forceinline__ void lds_add(float* p, float v) {
 // flushing pixel writes its id to the per-wave claim byte of its (xa,ya) window texel and reads it back (LDS executes a wave's
 // instructions in order): the pixel whose id survived adds non-atomically; the others on that texel and every pixel with
 // clamped corners use atomic adds, in a separate basic block.
+// (launch bound: the four blocks per CU that the LDS budget is made for, kWinFloats.  The kernel stands at 127 VGPRs, and the
+// compiler, not held to it, takes 129 once phase A is a helper: three waves per SIMD instead of four.)
 template <int C>
-struct BwdTile {      // pixels of a scatter tile: 16 x 4 (C = 16), 8 x 4 (C = 32), 4 x 4 (C = 64)
-  static constexpr int PPB = kThreads / (C / 4);
-  static constexpr int TH = 4, TW = PPB / TH;
-};
-
-template <int C>
-__global__ __launch_bounds__(kThreads) void warp_bwd_kernel(const TrainParams p) {
+__global__ __launch_bounds__(kThreads, 4) void warp_bwd_kernel(const TrainParams p) {
   constexpr int LPP = C / 4;            // lanes per pixel over the whole block
   constexpr int PPB = kThreads / LPP;   // pixels per tile = pixels per wave (every wave sees all of them)
   constexpr int LW = LPP / 4;           // lanes per pixel inside one wave (4 channels each)
   constexpr int G = C / 2;
-  constexpr int TW = BwdTile<C>::TW, TH = BwdTile<C>::TH;
   static_assert(PPB * LW == 64, "a wave holds every pixel of the tile");
-  static_assert(TW * TH == PPB, "tile shape");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   TapXY* tab = reinterpret_cast<TapXY*>(smem);
   float* win = reinterpret_cast<float*>(smem + (size_t)p.dchunk * p.n_src * PPB * sizeof(TapXY));
@@ -279,16 +212,12 @@ __global__ __launch_bounds__(kThreads) void warp_bwd_kernel(const TrainParams p)
   const int hw = p.g.h * p.g.w;
   const int W = p.g.w;
   const int b = blockIdx.y;
-  const int tile = (int)mdf::xcd_remap(blockIdx.x, p.nblk_x);
-  // a tile is BwdTile<C>::TW x TH pixels, not a run of a row: its taps' bounding box in a source map is (TW+1) x (TH+1) texels plus the
-  // depth sweep instead of a slanted (PPB+1)-texel line's box -- half the window texels to zero and flush, and a window that fits
-  const int tiles_x = (W + TW - 1) / TW;
-  const int tile_y0 = (tile / tiles_x) * TH, tile_x0 = (tile % tiles_x) * TW;
+  const BwdTile<C> pt((int)mdf::xcd_remap(blockIdx.x, p.nblk_x), W);
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int pl = lane / LW, sub = wave * LW + lane % LW;    // pixel of the tile, 4-channel slot of the pixel
-  const bool live = (tile_x0 + pl % TW) < W && (tile_y0 + pl / TW) < p.g.h;
-  const int pix = min(tile_y0 + pl / TW, p.g.h - 1) * W + min(tile_x0 + pl % TW, W - 1);
+  bool live;
+  const int pix = pt.pix(pl, W, p.g.h, live);
   volatile unsigned char* my_claim = claim[wave];
 
   float r[4];
@@ -318,47 +247,15 @@ __global__ __launch_bounds__(kThreads) void warp_bwd_kernel(const TrainParams p)
   for (int v_lo = 0; v_lo < p.n_src; v_lo += nv)
   for (int d0 = dlo; d0 < dhi; d0 += dstep) {
     const int nd = min(dstep, dhi - d0);
-    if (tid < 4 * p.n_src) bb[tid >> 2][tid & 3] = (tid & 1) ? INT32_MIN : INT32_MAX;
-    __syncthreads();
-    const int nent = nd * nv * PPB;
-    for (int e = tid; e < nent; e += kThreads) {
-      const int epl = e % PPB;
-      const int ev = v_lo + (e / PPB) % nv;
-      const int ed = e / (PPB * nv);
-      const bool elive = (tile_x0 + epl % TW) < W && (tile_y0 + epl / TW) < p.g.h;
-      const int yy = min(tile_y0 + epl / TW, p.g.h - 1), xx = min(tile_x0 + epl % TW, W - 1);
-      const int epix = yy * W + xx;
-      const float* m = p.proj + ((size_t)ev * p.B + b) * 12;
-      const int d = d0 + ed;
-      const float dep = p.hypos_per_pixel ? p.hypos[((size_t)b * p.D + d) * hw + epix] : p.hypos[(size_t)b * p.D + d];
-      float ix, iy;
-      warp_position(m, (float)xx, (float)yy, dep, p.g, ix, iy);
-      TapXY t;
-      tap_weights_corners(ix, iy, p.g, t.wt, t.xa, t.xb, t.ya, t.yb);
-      tab[e] = t;
-      if (elive) {
-        const bool a = (t.wt[0] != 0.0f) || (t.wt[2] != 0.0f), bq = (t.wt[1] != 0.0f) || (t.wt[3] != 0.0f);   // column xa / xb live
-        const bool cq = (t.wt[0] != 0.0f) || (t.wt[1] != 0.0f), dq = (t.wt[2] != 0.0f) || (t.wt[3] != 0.0f);  // row ya / yb live
-        if (a || bq) {
-          atomicMin(&bb[ev][0], a ? t.xa : t.xb);
-          atomicMax(&bb[ev][1], bq ? t.xb : t.xa);
-          atomicMin(&bb[ev][2], cq ? t.ya : t.yb);
-          atomicMax(&bb[ev][3], dq ? t.yb : t.ya);
-        }
-      }
-    }
-    __syncthreads();
+    fill_taps_bbox<PPB>(tab, bb, pt, p, b, d0, nd, v_lo, nv);
 
     for (int v = v_lo; v < v_lo + nv; ++v) {
-      const int xmin = bb[v][0], xmax = bb[v][1], ymin = bb[v][2], ymax = bb[v][3];
-      const int ww = xmax - xmin + 1, wh = ymax - ymin + 1;
-      const bool any = (xmax >= xmin) && (ymax >= ymin);
-      const bool use_win = any && ((long long)ww * wh * G <= kWinFloats);      // block-uniform
-      if (use_win) {
-        for (int i = tid; i < ww * wh * G; i += kThreads) win[i] = 0.0f;
+      const ScatterWin<G> w(bb[v]);
+      if (w.use) {
+        w.zero(win);
         __syncthreads();
       }
-      const char* sb = reinterpret_cast<const char*>(p.src[v] + (size_t)b * map_stride);     // uniform base + 32-bit lane offsets
+      const char* sb = reinterpret_cast<const char*>(p.src[v] + (size_t)b * map_stride);
       const unsigned lane_b = 16u * (unsigned)sub;
       float* gp = p.dsrc[v] + (size_t)b * gmap_stride + 2 * sub;
       const float4* ax = p.aux + (size_t)v * nvox;
@@ -366,17 +263,13 @@ __global__ __launch_bounds__(kThreads) void warp_bwd_kernel(const TrainParams p)
       const float mu = vpar[4 * v + 2], is = vpar[4 * v + 3];
       float pend0[4] = {0.f, 0.f, 0.f, 0.f}, pend1[4] = {0.f, 0.f, 0.f, 0.f};   // pending tap sums of the current corner set
       int cxa = -1, cxb = -1, cya = -1, cyb = -1;
-      // Tap liveness comes from the WEIGHTS (a tap whose weight was non-zero for some pending plane), never from the pending
-      // value: an out-of-bounds tap has weight 0 and lies outside the bounding box `bb` (built from the same weight test), but
-      // 0 * (non-finite gradient) = NaN would pass a value test and index the window out of range.  grid_sample's backward
-      // likewise adds nothing for out-of-bounds taps and propagates NaN through the in-bounds ones.
-      unsigned lm = 0;
+      unsigned lm = 0;    // live taps of the pending sums (warp_scatter.h, LIVENESS)
       auto flush_taps = [&](int xa, int xb, int ya, int yb) {
         bool plain = false;
         const unsigned m = lm;
         lm = 0;
-        if (use_win && !(p.all_atomic & 1)) {
-          const int slot = min(max((ya - ymin) * ww + (xa - xmin), 0), kWinFloats / 8 - 1);   // the window texel of (xa,ya): no false sharing
+        if (w.use && !(p.all_atomic & 1)) {
+          const int slot = min(max(w.texel(xa, ya), 0), kWinFloats / 8 - 1);   // the window texel of (xa,ya): no false sharing
           my_claim[slot] = (unsigned char)pl;
           plain = (my_claim[slot] == (unsigned char)pl) && (xb == xa + 1) && (yb == ya + 1);
         }
@@ -388,7 +281,7 @@ __global__ __launch_bounds__(kThreads) void warp_bwd_kernel(const TrainParams p)
           for (int k = 0; k < 4; ++k) {
             if (m & (1u << k)) {      // zero-weight (out-of-bounds) taps never leave the registers
               const int tx = (k & 1) ? xb : xa, ty = (k & 2) ? yb : ya;
-              float2* o = reinterpret_cast<float2*>(win + ((ty - ymin) * ww + (tx - xmin)) * G + 2 * sub);
+              float2* o = reinterpret_cast<float2*>(win + w.texel(tx, ty) * G + 2 * sub);
               float2 cur = *o;
               cur.x += a0[k]; cur.y += a1[k];
               *o = cur;
@@ -400,8 +293,8 @@ __global__ __launch_bounds__(kThreads) void warp_bwd_kernel(const TrainParams p)
           for (int k = 0; k < 4; ++k) {
             if (m & (1u << k)) {
               const int tx = (k & 1) ? xb : xa, ty = (k & 2) ? yb : ya;
-              if (use_win) {
-                float* o = win + ((ty - ymin) * ww + (tx - xmin)) * G + 2 * sub;
+              if (w.use) {
+                float* o = win + w.texel(tx, ty) * G + 2 * sub;
                 lds_add(o, a0[k]);
                 lds_add(o + 1, a1[k]);
               } else {
@@ -415,20 +308,13 @@ __global__ __launch_bounds__(kThreads) void warp_bwd_kernel(const TrainParams p)
       };
       for (int dd = 0; dd < nd; ++dd) {
         const TapXY t = tab[(dd * nv + (v - v_lo)) * PPB + pl];
-        const int o0 = (t.ya * W + t.xa), o1 = (t.ya * W + t.xb), o2 = (t.yb * W + t.xa), o3 = (t.yb * W + t.xb);
-        const float4 nw = *reinterpret_cast<const float4*>(sb + ((unsigned)o0 * (4u * C) + lane_b));
-        const float4 ne = *reinterpret_cast<const float4*>(sb + ((unsigned)o1 * (4u * C) + lane_b));
-        const float4 sw = *reinterpret_cast<const float4*>(sb + ((unsigned)o2 * (4u * C) + lane_b));
-        const float4 se = *reinterpret_cast<const float4*>(sb + ((unsigned)o3 * (4u * C) + lane_b));
+        float val[4];
+        gather_blend<C>(sb, t, W, lane_b, val);
         const size_t vox = ((size_t)b * p.D + d0 + dd) * hw + pix;
         const float4 sc = ax[vox];                                   // (w_v, dz_v, t_v, -)
         const float2 dc = *reinterpret_cast<const float2*>(p.dcost + vox * G + 2 * sub);
         const float dn = p.wsum[vox];
-        const float v0 = __fmaf_rn(se.x, t.wt[3], __fmaf_rn(sw.x, t.wt[2], __fmaf_rn(ne.x, t.wt[1], __fmul_rn(nw.x, t.wt[0]))));
-        const float v1 = __fmaf_rn(se.y, t.wt[3], __fmaf_rn(sw.y, t.wt[2], __fmaf_rn(ne.y, t.wt[1], __fmul_rn(nw.y, t.wt[0]))));
-        const float v2 = __fmaf_rn(se.z, t.wt[3], __fmaf_rn(sw.z, t.wt[2], __fmaf_rn(ne.z, t.wt[1], __fmul_rn(nw.z, t.wt[0]))));
-        const float v3 = __fmaf_rn(se.w, t.wt[3], __fmaf_rn(sw.w, t.wt[2], __fmaf_rn(ne.w, t.wt[1], __fmul_rn(nw.w, t.wt[0]))));
-        const float q0 = softmax2_p0(v0, v1), q1 = softmax2_p0(v2, v3);
+        const float q0 = softmax2_p0(val[0], val[1]), q1 = softmax2_p0(val[2], val[3]);
         const float sim0 = __fmaf_rn(q0, r[0], r[1]);
         const float sim1 = __fmaf_rn(q1, r[2], r[3]);
         const float wv = sc.x, dz = sc.y, tt = sc.z;
@@ -459,17 +345,9 @@ __global__ __launch_bounds__(kThreads) void warp_bwd_kernel(const TrainParams p)
         }
       }
       flush_taps(cxa, cxb, cya, cyb);
-      if (use_win) {
+      if (w.use) {
         __syncthreads();
-        float* gv = p.dsrc[v] + (size_t)b * gmap_stride;
-        for (int wy = 0; wy < wh; ++wy) {
-          float* grow = gv + ((size_t)(ymin + wy) * W + xmin) * G;     // ww*G contiguous floats
-          const float* wrow = win + wy * ww * G;
-          for (int j = tid; j < ww * G; j += kThreads) {
-            const float val = wrow[j];
-            if (val != 0.0f && !(p.all_atomic & 2)) unsafeAtomicAdd(grow + j, val);     // (bit 1: timing experiment, flush dropped)
-          }
-        }
+        if (!(p.all_atomic & 2)) w.flush(win, p.dsrc[v] + (size_t)b * gmap_stride, W);     // (bit 1: timing experiment, flush dropped)
         __syncthreads();
       }
     }
@@ -498,26 +376,9 @@ __global__ __launch_bounds__(kThreads) void warp_bwd_kernel(const TrainParams p)
   }
 }
 
-// A block walks its pixels over the planes one (plane, view) at a time, each step a dependent gather: with the few blocks of a
-// cfg3-sized map (432 at 72x96x64ch) the chip holds < 2 waves per SIMD and the kernel is latency-bound.  Cut the depth range
-// into slices (gridDim.z) until there are a few thousand blocks; per-pixel results that span the planes (d ref) meet through atomics.
-int depth_slices(TrainParams& p, int& dch, int target) {
-  const long long blocks = (long long)p.nblk_x * p.B;
-  int nz = (int)((target + blocks - 1) / blocks);
-  if (nz > p.D / 4) nz = p.D / 4;          // >= 4 planes per slice: a slice re-reads the reference features and the tap setup
-  if (nz < 1) nz = 1;
-  p.dslice = (p.D + nz - 1) / nz;
-  nz = (p.D + p.dslice - 1) / p.dslice;
-  if (dch > p.dslice) dch = p.dslice;
-  const int nch = (p.dslice + dch - 1) / dch;   // equal chunks inside a slice
-  dch = (p.dslice + nch - 1) / nch;
-  return nz;
-}
-
 int launch_bwd(TrainParams& p, int C, hipStream_t st) {
   const int lpp = C / 4, ppb = kThreads / lpp;
-  const int th = 4, tw = ppb / th;            // BwdTile<C>
-  p.nblk_x = ((p.g.w + tw - 1) / tw) * ((p.g.h + th - 1) / th);
+  p.nblk_x = bwd_tile_blocks(C, p.g.w, p.g.h);
   // tap-table entries per block: uniform hypotheses (stage 0) sweep an epipolar segment and amortise a view's window over more
   // planes; per-pixel hypotheses take a whole view's planes anyway
   static const int tab_env = [] { const char* e = getenv("MDF_WARP_BWD_TAB"); return (e && atoi(e) > 0) ? atoi(e) : 0; }();   // dev A/B
@@ -529,10 +390,10 @@ int launch_bwd(TrainParams& p, int C, hipStream_t st) {
   // 178 us unsliced, 284 in two slices); uniform hypotheses (stage 0, 432 blocks at cfg3) take three slices (162 us; 192 in two)
   static const int target_env = [] { const char* e = getenv("MDF_WARP_BWD_BLOCKS"); return (e && atoi(e) > 0) ? atoi(e) : 0; }();   // dev A/B
   const int nz = depth_slices(p, dch, target_env ? target_env : (p.hypos_per_pixel ? 768 : 1024));
-  p.dchunk = dch;
+  p.dchunk = equal_chunks(p.dslice, dch);
   const char* dbg = getenv("MDF_WARP_BWD_ATOMIC");      // read per call: tests flip it inside one process
   p.all_atomic = (dbg && atoi(dbg) > 0) ? atoi(dbg) : 0;     // bit 0: all-atomic window updates; bit 1: timing experiment without the flush
-  const size_t lds = (size_t)dch * p.n_src * ppb * sizeof(TapXY) + (size_t)kWinFloats * sizeof(float);
+  const size_t lds = (size_t)p.dchunk * p.n_src * ppb * sizeof(TapXY) + (size_t)kWinFloats * sizeof(float);
   dim3 grid(p.nblk_x, p.B, nz), block(kThreads);
   switch (C) {
     case 64: hipLaunchKernelGGL((warp_bwd_kernel<64>), grid, block, lds, st, p); break;
@@ -553,8 +414,8 @@ int launch_train(TrainParams& p, int C, hipStream_t st) {
   if (dch < 1) dch = 1;
   static const int target_env = [] { const char* e = getenv("MDF_WARP_TRAIN_BLOCKS"); return (e && atoi(e) > 0) ? atoi(e) : 0; }();   // dev A/B
   const int nz = depth_slices(p, dch, target_env ? target_env : (p.hypos_per_pixel ? 1024 : 2048));
-  p.dchunk = dch;
-  const size_t lds = (size_t)dch * p.n_src * ppb * sizeof(TapEntry);
+  p.dchunk = equal_chunks(p.dslice, dch);
+  const size_t lds = (size_t)p.dchunk * p.n_src * ppb * sizeof(TapEntry);
   dim3 grid(p.nblk_x, p.B, nz), block(kThreads);
   switch (C) {
     case 64: hipLaunchKernelGGL((warp_train_kernel<64, PASS>), grid, block, lds, st, p); break;
@@ -625,16 +486,12 @@ extern "C" int mdf_warp_aggregate_vec_train(int pass, const float* ref_fea, cons
                                             int n_src, void* stream) {
   MDF_REQUIRE(ref_fea && src_feas && proj && hypos && par, "null pointer argument");
   MDF_REQUIRE(pass >= 0 && pass <= 3, "pass=%d not in 0..3", pass);
-  MDF_REQUIRE(B > 0 && D > 0 && h > 1 && w > 1, "bad shape B=%d D=%d h=%d w=%d", B, D, h, w);
-  MDF_REQUIRE((long long)h * w * C < (1ll << 30), "feature map too large for 32-bit byte offsets");
-  MDF_REQUIRE(n_src >= 1 && n_src <= MDF_MAX_SRC_VIEWS, "n_src=%d out of range [1,%d]", n_src, MDF_MAX_SRC_VIEWS);
+  if (int rc = check_shape(B, D, h, w, C)) return rc;
+  if (int rc = check_n_src(n_src)) return rc;
   if (G * 2 != C) return mdf::fail(MDF_EUNSUPPORTED, "only C/G == 2 is built (C=%d, G=%d)", C, G);
   TrainParams p{};
   p.ref = ref_fea;
-  for (int v = 0; v < n_src; ++v) {
-    MDF_REQUIRE(src_feas[v], "src_feas[%d] is null", v);
-    p.src[v] = src_feas[v];
-  }
+  if (int rc = copy_views(p.src, src_feas, n_src, "src_feas")) return rc;
   p.proj = proj; p.hypos = hypos; p.par = par; p.red_in = red_in; p.dcost = dcost; p.cost = cost; p.wsum = wsum;
   p.red_out = red_out; p.dref = dref; p.dcw = dcw; p.aux = reinterpret_cast<float4*>(aux);
   p.g = make_geom(h, w);
@@ -652,10 +509,7 @@ extern "C" int mdf_warp_aggregate_vec_train(int pass, const float* ref_fea, cons
       return launch_train<kBwdReduce>(p, C, st);
     default:
       MDF_REQUIRE(dcost && wsum && red_in && dref && dsrc && dcw && aux, "backward pass needs dcost, wsum, red_in, dref, dsrc, dcw, aux");
-      for (int v = 0; v < n_src; ++v) {
-        MDF_REQUIRE(dsrc[v], "dsrc[%d] is null", v);
-        p.dsrc[v] = dsrc[v];
-      }
+      if (int rc = copy_views(p.dsrc, dsrc, n_src, "dsrc")) return rc;
       return launch_bwd(p, C, st);
   }
 }

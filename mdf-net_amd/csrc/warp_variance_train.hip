@@ -12,20 +12,17 @@
 // m is RECOMPUTED per voxel from the features (a stored sum volume would be as large as the cost volume): per chunk of at most
 // kPlanes depth planes a lane first gathers every view and keeps m and (2/N) g of its 4 channels in registers, then walks the
 // views again, one at a time, and scatters.  Thread mapping of the eval kernel (a lane owns 4 channels, the C/4 lanes of a pixel
-// are neighbours and reduce with DPP row operations); tile shape, LDS window, dense flush and direct-to-memory fallback of
-// warp_bwd_kernel (warp_aggregate_train.hip).  Every channel carries a gradient of its own here, so a window texel is C floats
-// and all window updates are LDS float atomics (no claim bytes: the four waves of a block hold DIFFERENT pixels of the tile).
+// are neighbours and reduce with DPP row operations); the scatter -- tile shape, tap table with bounding boxes, LDS window, dense
+// flush and direct-to-memory fallback -- is warp_scatter.h's, shared with warp_bwd_kernel.  Every channel carries a gradient of
+// its own here, so a window texel is C floats and all window updates are LDS float atomics (no claim bytes: the four waves of a
+// block hold DIFFERENT pixels of the tile).  The window (kWinFloats, 16 KiB) lies next to a tap table of at most 32 KiB.
 //
 // Compile with -ffp-contract=off like the other warp kernels: the sample positions are those of warp_position.
 #include <cstdlib>
-#include "warp_common.h"
+#include "warp_scatter.h"
 
 namespace {
 
-#ifndef MDF_VAR_BWD_WIN_FLOATS
-#define MDF_VAR_BWD_WIN_FLOATS 4096
-#endif
-constexpr int kWinFloats = MDF_VAR_BWD_WIN_FLOATS;   // 16 KiB next to the tap table (at most 32 KiB)
 constexpr int kPlanes = 4;                           // depth planes per chunk whose m and g stay in registers (32 VGPRs)
 
 struct VarBwdParams {
@@ -40,42 +37,11 @@ struct VarBwdParams {
   int B, D, n_src, hypos_per_pixel, dout_ndhwc, dchunk, dslice, nblk_x;
 };
 
-__device__ __forceinline__ void lds_add(float* p, float v) {     // ds_add_f32 (see warp_aggregate_train.hip)
-  (void)__hip_atomic_fetch_add((__attribute__((address_space(3))) float*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-template <int C>
-__device__ __forceinline__ void gather_blend(const char* sb, const TapXY& t, int W, unsigned lane_b, float* val) {
-  const int o0 = (t.ya * W + t.xa), o1 = (t.ya * W + t.xb), o2 = (t.yb * W + t.xa), o3 = (t.yb * W + t.xb);
-  const float4 nw = *reinterpret_cast<const float4*>(sb + ((unsigned)o0 * (4u * C) + lane_b));
-  const float4 ne = *reinterpret_cast<const float4*>(sb + ((unsigned)o1 * (4u * C) + lane_b));
-  const float4 sw = *reinterpret_cast<const float4*>(sb + ((unsigned)o2 * (4u * C) + lane_b));
-  const float4 se = *reinterpret_cast<const float4*>(sb + ((unsigned)o3 * (4u * C) + lane_b));
-  val[0] = __fmaf_rn(se.x, t.wt[3], __fmaf_rn(sw.x, t.wt[2], __fmaf_rn(ne.x, t.wt[1], __fmul_rn(nw.x, t.wt[0]))));
-  val[1] = __fmaf_rn(se.y, t.wt[3], __fmaf_rn(sw.y, t.wt[2], __fmaf_rn(ne.y, t.wt[1], __fmul_rn(nw.y, t.wt[0]))));
-  val[2] = __fmaf_rn(se.z, t.wt[3], __fmaf_rn(sw.z, t.wt[2], __fmaf_rn(ne.z, t.wt[1], __fmul_rn(nw.z, t.wt[0]))));
-  val[3] = __fmaf_rn(se.w, t.wt[3], __fmaf_rn(sw.w, t.wt[2], __fmaf_rn(ne.w, t.wt[1], __fmul_rn(nw.w, t.wt[0]))));
-}
-
-// softmax over all C channels of a pixel, the arithmetic of warp_kernel<C,kVar>
-template <int LPP>
-__device__ __forceinline__ void softmax_pixel(const float* val, float* pr) {
-  const float mx = pixel_max<LPP>(fmaxf(fmaxf(val[0], val[1]), fmaxf(val[2], val[3])));
-  float e[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) e[k] = expf(val[k] - mx);
-  const float den = pixel_sum<LPP>((e[0] + e[1]) + (e[2] + e[3]));
-#pragma unroll
-  for (int k = 0; k < 4; ++k) pr[k] = e[k] / den;
-}
-
 // VAR = true: variance aggregation (ref + n_src views).  VAR = false: homo_warping of one view, gv = g.
 template <int C, bool VAR>
 __global__ __launch_bounds__(kThreads) void warp_var_bwd_kernel(const VarBwdParams p) {
   constexpr int LPP = C / 4;            // lanes per pixel (neighbours inside one DPP row)
   constexpr int PPB = kThreads / LPP;   // pixels per tile
-  constexpr int TH = 4, TW = PPB / TH;  // 16 x 4 (C = 16), 8 x 4 (C = 32), 4 x 4 (C = 64): a compact footprint in the source maps
-  static_assert(TW * TH == PPB, "tile shape");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   TapXY* tab = reinterpret_cast<TapXY*>(smem);
   float* win = reinterpret_cast<float*>(smem + (size_t)p.dchunk * p.n_src * PPB * sizeof(TapXY));
@@ -84,13 +50,11 @@ __global__ __launch_bounds__(kThreads) void warp_var_bwd_kernel(const VarBwdPara
   const int hw = p.g.h * p.g.w;
   const int W = p.g.w;
   const int b = blockIdx.y;
-  const int tile = (int)mdf::xcd_remap(blockIdx.x, p.nblk_x);
-  const int tiles_x = (W + TW - 1) / TW;
-  const int tile_y0 = (tile / tiles_x) * TH, tile_x0 = (tile % tiles_x) * TW;
+  const BwdTile<C> pt((int)mdf::xcd_remap(blockIdx.x, p.nblk_x), W);
   const int tid = threadIdx.x;
   const int pl = tid / LPP, sub = tid % LPP;
-  const bool live = (tile_x0 + pl % TW) < W && (tile_y0 + pl / TW) < p.g.h;
-  const int pix = min(tile_y0 + pl / TW, p.g.h - 1) * W + min(tile_x0 + pl % TW, W - 1);
+  bool live;
+  const int pix = pt.pix(pl, W, p.g.h, live);
 
   float r[4] = {0.f, 0.f, 0.f, 0.f};
   if (VAR) {
@@ -106,37 +70,8 @@ __global__ __launch_bounds__(kThreads) void warp_var_bwd_kernel(const VarBwdPara
   const int dlo = blockIdx.z * p.dslice, dhi = min(p.D, dlo + p.dslice);
   for (int d0 = dlo; d0 < dhi; d0 += p.dchunk) {
     const int nd = min(p.dchunk, dhi - d0);      // <= kPlanes
-    if (tid < 4 * p.n_src) bb[tid >> 2][tid & 3] = (tid & 1) ? INT32_MIN : INT32_MAX;
-    __syncthreads();
     // ---------------- tap table of the chunk, all views, and the bounding box of every view's live taps
-    const int nent = nd * p.n_src * PPB;
-    for (int e = tid; e < nent; e += kThreads) {
-      const int epl = e % PPB;
-      const int ev = (e / PPB) % p.n_src;
-      const int ed = e / (PPB * p.n_src);
-      const bool elive = (tile_x0 + epl % TW) < W && (tile_y0 + epl / TW) < p.g.h;
-      const int yy = min(tile_y0 + epl / TW, p.g.h - 1), xx = min(tile_x0 + epl % TW, W - 1);
-      const int epix = yy * W + xx;
-      const float* m = p.proj + ((size_t)ev * p.B + b) * 12;
-      const int d = d0 + ed;
-      const float dep = p.hypos_per_pixel ? p.hypos[((size_t)b * p.D + d) * hw + epix] : p.hypos[(size_t)b * p.D + d];
-      float ix, iy;
-      warp_position(m, (float)xx, (float)yy, dep, p.g, ix, iy);
-      TapXY t;
-      tap_weights_corners(ix, iy, p.g, t.wt, t.xa, t.xb, t.ya, t.yb);
-      tab[e] = t;
-      if (elive) {
-        const bool a = (t.wt[0] != 0.0f) || (t.wt[2] != 0.0f), bq = (t.wt[1] != 0.0f) || (t.wt[3] != 0.0f);   // column xa / xb live
-        const bool cq = (t.wt[0] != 0.0f) || (t.wt[1] != 0.0f), dq = (t.wt[2] != 0.0f) || (t.wt[3] != 0.0f);  // row ya / yb live
-        if (a || bq) {
-          atomicMin(&bb[ev][0], a ? t.xa : t.xb);
-          atomicMax(&bb[ev][1], bq ? t.xb : t.xa);
-          atomicMin(&bb[ev][2], cq ? t.ya : t.yb);
-          atomicMax(&bb[ev][3], dq ? t.yb : t.ya);
-        }
-      }
-    }
-    __syncthreads();
+    fill_taps_bbox<PPB>(tab, bb, pt, p, b, d0, nd, 0, p.n_src);
 
     // ---------------- phase 1: (2/N) g and the mean over the views of every plane of the chunk, in registers
     float g2[kPlanes][4], mean[kPlanes][4];
@@ -177,12 +112,9 @@ __global__ __launch_bounds__(kThreads) void warp_var_bwd_kernel(const VarBwdPara
 
     // ---------------- phase 2: one view at a time, the scatter through its window
     for (int v = 0; v < p.n_src; ++v) {
-      const int xmin = bb[v][0], xmax = bb[v][1], ymin = bb[v][2], ymax = bb[v][3];
-      const int ww = xmax - xmin + 1, wh = ymax - ymin + 1;
-      const bool any = (xmax >= xmin) && (ymax >= ymin);
-      const bool use_win = any && ((long long)ww * wh * C <= kWinFloats);      // block-uniform
-      if (use_win) {
-        for (int i = tid; i < ww * wh * C; i += kThreads) win[i] = 0.0f;
+      const ScatterWin<C> w(bb[v]);
+      if (w.use) {
+        w.zero(win);
         __syncthreads();
       }
       const char* sb = VAR ? reinterpret_cast<const char*>(p.src[v] + (size_t)b * map_stride) : nullptr;
@@ -191,9 +123,7 @@ __global__ __launch_bounds__(kThreads) void warp_var_bwd_kernel(const VarBwdPara
 #pragma unroll
       for (int k = 0; k < 4; ++k) { pend[k][0] = 0.f; pend[k][1] = 0.f; pend[k][2] = 0.f; pend[k][3] = 0.f; }
       int cxa = -1, cxb = -1, cya = -1, cyb = -1;
-      // Tap liveness comes from the WEIGHTS and the integer corners, never from the pending value (warp_bwd_kernel): an
-      // out-of-bounds tap has weight 0 and lies outside `bb`; 0 * (non-finite gradient) = NaN must not index the window.
-      unsigned lm = 0;
+      unsigned lm = 0;    // live taps of the pending sums (warp_scatter.h, LIVENESS)
       auto flush_taps = [&](int xa, int xb, int ya, int yb) {
         const unsigned m = lm;
         lm = 0;
@@ -201,8 +131,8 @@ __global__ __launch_bounds__(kThreads) void warp_var_bwd_kernel(const VarBwdPara
         for (int k = 0; k < 4; ++k) {
           if (m & (1u << k)) {
             const int tx = (k & 1) ? xb : xa, ty = (k & 2) ? yb : ya;
-            if (use_win) {
-              float* o = win + ((ty - ymin) * ww + (tx - xmin)) * C + 4 * sub;
+            if (w.use) {
+              float* o = win + w.texel(tx, ty) * C + 4 * sub;
               lds_add(o, pend[k][0]); lds_add(o + 1, pend[k][1]); lds_add(o + 2, pend[k][2]); lds_add(o + 3, pend[k][3]);
             } else {
               float* o = gout + (size_t)(ty * W + tx) * C;
@@ -247,17 +177,9 @@ __global__ __launch_bounds__(kThreads) void warp_var_bwd_kernel(const VarBwdPara
         }
       }
       flush_taps(cxa, cxb, cya, cyb);
-      if (use_win) {
+      if (w.use) {
         __syncthreads();
-        float* gmap = p.dsrc[v] + (size_t)b * map_stride;
-        for (int wy = 0; wy < wh; ++wy) {
-          float* grow = gmap + ((size_t)(ymin + wy) * W + xmin) * C;     // ww*C contiguous floats: dense global atomics
-          const float* wrow = win + wy * ww * C;
-          for (int j = tid; j < ww * C; j += kThreads) {
-            const float val = wrow[j];
-            if (val != 0.0f) unsafeAtomicAdd(grow + j, val);             // (NaN != 0: non-finite sums are sent on)
-          }
-        }
+        w.flush(win, p.dsrc[v] + (size_t)b * map_stride, W);
         __syncthreads();
       }
     }
@@ -277,21 +199,15 @@ __global__ __launch_bounds__(kThreads) void warp_var_bwd_kernel(const VarBwdPara
 template <bool VAR>
 int launch_var_bwd(VarBwdParams& p, int C, hipStream_t st) {
   const int lpp = C / 4, ppb = kThreads / lpp;
-  const int th = 4, tw = ppb / th;
-  p.nblk_x = ((p.g.w + tw - 1) / tw) * ((p.g.h + th - 1) / th);
+  p.nblk_x = bwd_tile_blocks(C, p.g.w, p.g.h);
   static const int tab_env = [] { const char* e = getenv("MDF_VAR_BWD_TAB"); return (e && atoi(e) > 0) ? atoi(e) : 1024; }();   // dev A/B
   int dch = tab_env / (p.n_src * ppb);        // tap-table entries (32 B each) per block
   if (dch > kPlanes) dch = kPlanes;
   if (dch < 1) dch = 1;
-  // depth slices (gridDim.z): the small maps of the first stage give a few hundred blocks only (warp_aggregate_train.hip:depth_slices)
+  // depth slices (gridDim.z): the small maps of the first stage give a few hundred blocks only.  The chunks of a slice are not
+  // equalised here (equal_chunks): they are at most kPlanes planes anyway
   static const int target_env = [] { const char* e = getenv("MDF_VAR_BWD_BLOCKS"); return (e && atoi(e) > 0) ? atoi(e) : 1024; }();   // dev A/B
-  const long long blocks = (long long)p.nblk_x * p.B;
-  int nz = (int)((target_env + blocks - 1) / blocks);
-  if (nz > p.D / 4) nz = p.D / 4;
-  if (nz < 1) nz = 1;
-  p.dslice = (p.D + nz - 1) / nz;
-  nz = (p.D + p.dslice - 1) / p.dslice;
-  if (dch > p.dslice) dch = p.dslice;
+  const int nz = depth_slices(p, dch, target_env);
   p.dchunk = dch;
   const size_t lds = (size_t)dch * p.n_src * ppb * sizeof(TapXY) + (size_t)kWinFloats * sizeof(float);
   dim3 grid(p.nblk_x, p.B, nz), block(kThreads);
@@ -304,13 +220,9 @@ int launch_var_bwd(VarBwdParams& p, int C, hipStream_t st) {
   return mdf::check_launch("warp_var_bwd_kernel");
 }
 
-int check_shape(int B, int C, int D, int h, int w) {
-  MDF_REQUIRE(B > 0 && D > 0 && h > 1 && w > 1, "bad shape B=%d D=%d h=%d w=%d", B, D, h, w);
-  MDF_REQUIRE(B < 65536, "B=%d too large for one launch", B);
-  MDF_REQUIRE((long long)h * w * C < (1ll << 30), "feature map too large for 32-bit byte offsets");
-  if (C != 16 && C != 32 && C != 64)
-    return mdf::fail(MDF_EUNSUPPORTED, "C=%d not supported (built for 16, 32, 64)", C);
-  return MDF_OK;
+int check_var_bwd(int B, int C, int D, int h, int w) {
+  if (int rc = check_shape(B, D, h, w, C, 65536)) return rc;
+  return check_channels(C);
 }
 
 }  // namespace
@@ -319,11 +231,11 @@ extern "C" int mdf_warp_aggregate_var_bwd(const float* ref_fea, const float* con
                                           int hypos_per_pixel, const float* dcost, float* dref, float* const* dsrc, int B, int C, int D,
                                           int h, int w, int n_src, void* stream) {
   MDF_REQUIRE(ref_fea && src_feas && proj && hypos && dcost && dref && dsrc, "null pointer argument");
-  if (int rc = check_shape(B, C, D, h, w)) return rc;
-  MDF_REQUIRE(n_src >= 1 && n_src <= MDF_MAX_SRC_VIEWS, "n_src=%d out of range [1,%d]", n_src, MDF_MAX_SRC_VIEWS);
+  if (int rc = check_var_bwd(B, C, D, h, w)) return rc;
+  if (int rc = check_n_src(n_src)) return rc;
   VarBwdParams p{};
   p.ref = ref_fea;
-  for (int v = 0; v < n_src; ++v) {
+  for (int v = 0; v < n_src; ++v) {     // (one message for both arrays: not copy_views)
     MDF_REQUIRE(src_feas[v] && dsrc[v], "src_feas[%d] or dsrc[%d] is null", v, v);
     p.src[v] = src_feas[v];
     p.dsrc[v] = dsrc[v];
@@ -337,7 +249,7 @@ extern "C" int mdf_warp_aggregate_var_bwd(const float* ref_fea, const float* con
 extern "C" int mdf_homo_warp_bwd(const float* dvol, int vol_layout, const float* proj, const float* hypos, int hypos_per_pixel,
                                  float* dsrc, int B, int C, int D, int h, int w, void* stream) {
   MDF_REQUIRE(dvol && proj && hypos && dsrc, "null pointer argument");
-  if (int rc = check_shape(B, C, D, h, w)) return rc;
+  if (int rc = check_var_bwd(B, C, D, h, w)) return rc;
   MDF_REQUIRE(vol_layout == MDF_VOL_NCDHW || vol_layout == MDF_VOL_NDHWC, "vol_layout=%d", vol_layout);
   VarBwdParams p{};
   p.dsrc[0] = dsrc;

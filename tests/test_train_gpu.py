@@ -351,6 +351,47 @@ def test_vector_aggregate_training_forward_backward(stage, b, h, w, nviews, per_
         assert _rel(pa.grad, r32["grads"][k]) < (5e-4 if pa.numel() > 1 else 1e-2), k
 
 
+def test_vector_aggregate_scatter_window_and_direct_to_memory_paths():
+    """Both ways of warp_bwd_kernel's scatter in one launch: tiles whose taps fit the LDS window and tiles that scatter to memory
+    directly.  Reference projection = identity and source views that magnify 2x..6x over the per-pixel depth range (the relative
+    projection is the source matrix, in pixel units): near the map's origin a 4 x 4 tile's taps cover more than the 128 texels a
+    window holds at 32 groups, further out they leave the frame.  Oracle and bars of test_vector_aggregate_training_forward_backward.
+    The arithmetic for view 0 (tz = -420, magnification d / (d - 420) = 6.25 at d = 500 down to 2.1 at d = 800, per-pixel d anywhere
+    between): the tile at the origin (x, y in 0..3) maps to x' = 0..18.75, y' = 0..18.75, clamped into the 15 x 13 map: a live box of
+    15 x 13 = 195 texels, above both window sizes (4096 floats / 64 channels = 64 texels, / 32 groups = 128 texels) -> direct to
+    memory.  The tile at x0 = 4, y0 = 4 maps to x' >= 8.4, y' >= 8.4, in frame only up to 14 and 12: at most 7 x 5 = 35 texels ->
+    window.  (Also run once with a library built with a 64-float window, where every footprint takes the direct path.)"""
+    from net.unit.homoaggregate import VectorAggregate
+    from oracle import train_check as TC
+    h, w, c, g, d = 13, 15, 64, 32, 5
+    torch.manual_seed(5)
+    mod = VectorAggregate(g)
+    with torch.no_grad():
+        for p in mod.parameters():
+            p.add_(0.3 * torch.randn_like(p))
+    sd = {k: v.clone() for k, v in mod.state_dict().items()}
+
+    def cam(t):
+        m = torch.eye(4)
+        m[:3, 3] = torch.tensor(t)
+        return m.unsqueeze(0)
+    rp, sps = torch.eye(4).unsqueeze(0), [cam([0.0, 0.0, -420.0]), cam([10.0, -5.0, -400.0])]
+    feats = [torch.randn(1, c, h, w) for _ in range(3)]
+    hyp = 500 + 300 * torch.rand(1, d, h, w)
+    dcost = torch.randn(1, g, d, h, w)
+    r32 = TC.aggregate(sd, g, feats, rp, sps, hyp, dcost, torch.float32)
+    mod.train().to(DEV)
+    fd = [f.to(DEV).requires_grad_(True) for f in feats]
+    cost = mod(fd, rp.to(DEV), tuple(s.to(DEV) for s in sps), hyp.to(DEV))
+    e_cost = _rel(cost, r32["cost"])
+    cost.backward(dcost.to(DEV))
+    e_grads = [_rel(a_.grad, r_) for a_, r_ in zip(fd, r32["dfeats"])]
+    print(f"\ncost {e_cost:.1e}, d feats {[f'{e:.1e}' for e in e_grads]}")
+    assert cost.shape == r32["cost"].shape and e_cost < 2e-5
+    for i, e in enumerate(e_grads):
+        assert e < 2e-4, f"feature {i}: {e}"
+
+
 def _aggregate_case(stage, width, height, nviews, seed, hyp_spread=20.0):
     """Homoaggre[stage] in training mode at the stage's share of a width x height item: (module, device inputs)."""
     from net.unit.homoaggregate import VectorAggregate

@@ -179,6 +179,48 @@ def test_ragged_and_edge_shapes(h, w, c, nsrc, d, seed):
     assert _rel(sd.grad, w32["dsrc"]) < 2e-4
 
 
+def _magnifying_cameras():
+    """Reference projection = identity, so the relative projection is the source matrix itself, in pixel units: x' = (x d + tx) /
+    (d + tz).  With tz close to -d a source view magnifies 2x..6x over the depth range 500..800, so the taps of a 4 x 4 pixel tile
+    over one chunk of planes cover more texels than the scatter's LDS window holds near the map's origin (the direct-to-memory
+    path), and run out of frame further out (windows of the few live taps).
+    The arithmetic for view 0 (tz = -420, magnification d / (d - 420) = 6.25 at d = 500 down to 2.1 at d = 800, per-pixel d anywhere
+    between): the tile at the origin (x, y in 0..3) maps to x' = 0..18.75, y' = 0..18.75, clamped into the 15 x 13 map: a live box of
+    15 x 13 = 195 texels, above both window sizes (4096 floats / 64 channels = 64 texels, / 32 groups = 128 texels) -> direct to
+    memory.  The tile at x0 = 4, y0 = 4 maps to x' >= 8.4, y' >= 8.4, in frame only up to 14 and 12: at most 7 x 5 = 35 texels ->
+    window.  (Also run once with a library built with a 64-float window, where every footprint takes the direct path.)"""
+    def cam(t):
+        m = torch.eye(4)
+        m[:3, 3] = torch.tensor(t)
+        return m.unsqueeze(0)
+    return torch.eye(4).unsqueeze(0), [cam([0.0, 0.0, -420.0]), cam([10.0, -5.0, -400.0])]
+
+
+def test_scatter_window_and_direct_to_memory_paths():
+    """Both ways of the scatter in one launch, for the variance backward and the stand-alone warp backward: tiles whose footprint
+    fits the LDS window and tiles that scatter to memory directly (13 x 15 map, 64 channels: a window holds 64 texels).  Same
+    oracle and bars as test_ragged_and_edge_shapes."""
+    from net.unit.base import homo_warping
+    h, w, c, d = 13, 15, 64, 5
+    rng = np.random.RandomState(5)
+    rp, sps = _magnifying_cameras()
+    feats = [T(rng.randn(1, c, h, w).astype(np.float32)) for _ in range(3)]
+    hyp = T((500 + 300 * rng.rand(1, d, h, w)).astype(np.float32))
+    dcost = T(rng.randn(1, c, d, h, w).astype(np.float32))
+    r32 = _oracle_variance(feats, rp, sps, hyp, dcost, torch.float32)
+    cost, fd = _run_slot(feats, rp, sps, hyp, dcost)
+    e_cost, e_grads = _rel(cost, r32["cost"]), [_rel(a.grad, r_) for a, r_ in zip(fd, r32["dfeats"])]
+    w32 = _oracle_warp(feats[1], sps[0], rp, hyp, dcost, torch.float32)
+    sd = feats[1].to(DEV).requires_grad_(True)
+    homo_warping(sd, sps[0].to(DEV), rp.to(DEV), hyp.to(DEV)).backward(dcost.to(DEV))
+    e_warp = _rel(sd.grad, w32["dsrc"])
+    print(f"\ncost {e_cost:.1e}, d feats {[f'{e:.1e}' for e in e_grads]}, warp d src {e_warp:.1e}")
+    assert e_cost < 2e-5
+    for i, e in enumerate(e_grads):
+        assert e < 2e-4, f"feature {i}: {e}"
+    assert e_warp < 2e-4
+
+
 # ----------------------------------------------------------------------------------------------- 4. non-finite upstream gradient
 @pytest.mark.parametrize("stage", [0, 2])
 def test_nonfinite_upstream_gradient_propagates_like_the_oracle(stage):

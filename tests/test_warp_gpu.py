@@ -92,8 +92,11 @@ def test_variance_aggregate_vs_reference_golden(golden):
 
 
 def test_ragged_and_edge_shapes(seeded_sd):
-    """Pixel counts that are not multiples of the block tile, 1 and 10 source views, D=1."""
-    for (h, w, c, nsrc, d, seed) in [(7, 9, 64, 1, 1, 1), (13, 11, 32, 10, 3, 2), (5, 31, 16, 2, 5, 3)]:
+    """Pixel counts that are not multiples of the block tile, 1 and 10 source views, D=1; and both forms of the tap-table fill of
+    every kernel these shapes select: 3 source views at 16 channels (the generic fill of the 4-channel kernel: 64 x 3 pairs do not
+    divide the block), 8 at 32 channels (two pairs per thread in the 8-channel kernel), on a 5 x 7 map ragged against every tile."""
+    for (h, w, c, nsrc, d, seed) in [(7, 9, 64, 1, 1, 1), (13, 11, 32, 10, 3, 2), (5, 31, 16, 2, 5, 3), (5, 7, 16, 3, 5, 4),
+                                     (5, 7, 32, 8, 5, 5)]:
         rng = np.random.RandomState(seed)
         stage = {64: 0, 32: 1, 16: 2}[c]
         intr, extr, dr = synth.make_cameras(w * 2 ** (3 - stage), h * 2 ** (3 - stage), nsrc + 1, batch=1,
