@@ -924,7 +924,7 @@ __host__ __device__ inline bool wino2d_built(int Cin, int Cout) {   // ((16, 32)
 }
 __host__ __device__ inline bool wd_built(int Cin, int Cout) { return Cout == 8 && (Cin == 8 || Cin == 16); }   // 3-D, depth-pair Winograd
 // 2-D k5 s2 layers that also run as a Winograd 3x3 conv over the four parity images of their input (conv_lds.hip, LdsConvParams::s2d)
-__host__ __device__ inline bool k5w_built(int Cin, int Cout) { return (Cin == 16 && Cout == 32) || (Cin == 8 && Cout == 16); }
+__host__ __device__ inline bool k5w_built(int Cin, int Cout) { return (Cin == 32 && Cout == 64) || (Cin == 16 && Cout == 32) || (Cin == 8 && Cout == 16); }
 __host__ __device__ inline int padded_cin(int c) { return c <= 4 ? 4 : c; }
 
 // One complete packed weight set, as mdf_conv3d_pack_weights / mdf_conv_pack_weights lay it out: the plain fragments, then

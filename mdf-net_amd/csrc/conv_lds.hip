@@ -976,17 +976,19 @@ int mdf_conv_lds_dispatch(const float* x, const float* wpack, const float* alpha
   const int pad = (KHW - 1) / 2;
   p.Ho = (H + 2 * pad - KHW) / stride + 1;
   p.Wo = (W + 2 * pad - KHW) / stride + 1;
-  // The 2-D k5 s2 layer 16 -> 32 as a Winograd 3x3 conv over the four parity images of its input (64 -> 32: 16 instead of 25 MFMA groups per
-  // input channel; 163 -> 141 us); the transform-domain fragments follow the 25 plain taps (conv3d.hip: k5w_built).  (8 -> 16 the same way,
-  // 32 -> 16 over the parity images, measured 200 against 203 us -- that layer waits on HBM, and one block per CU does not help it; 32 -> 64
-  // would need 128 input channels in LDS.)
+  // The 2-D k5 s2 layers as a Winograd 3x3 conv over the four parity images of their input (16 -> 32 is 64 -> 32: 16 instead of 25 MFMA groups
+  // per input channel, direct 163 -> 141 us; wino2d.hip then skips the groups whose weights are structurally zero, 12.25 per input channel:
+  // 140 -> 114 us, profiles/r07_bench_cfg2.md); the transform-domain fragments follow the 25 plain taps (conv3d.hip: k5w_built).  (8 -> 16
+  // and 32 -> 64 the same way; 32 -> 64 walks its 128 logical channels in two passes over the LDS plane of 64: direct 159 -> 127 us.  32 -> 16 over the parity images, measured 200 against 203 us -- that layer waits on HBM, and
+  // one block per CU does not help it.)
   {
     const bool k5w = [] { const char* e = getenv("MDF_CONV_K5_WINOGRAD"); return e ? atoi(e) != 0 : true; }();   // dev A/B (read per call)
     if (use_wg && k5w && KD == 1 && KHW == 5 && stride == 2 && !stat && !res_up && !shuffle2 && !planar_in && H % 2 == 0 && W % 2 == 0) {
-      // (wino2d.hip's S2D form first: pinned accumulators, one transform cluster per chunk -- 16 -> 32 and, there, 8 -> 16 too)
+      // (wino2d.hip's S2D form first: pinned accumulators, one transform cluster per chunk -- 16 -> 32 and, there only, 8 -> 16 and 32 -> 64)
       const bool use_w2 = [] { const char* e = getenv("MDF_CONV_WINO2D"); return e ? atoi(e) != 0 : true; }();
-      if (use_w2 && !res && Cin == Cin_mem && ((Cin == 16 && Cout == 32) || (Cin == 8 && Cout == 16))) {
-        const size_t plain = (size_t)25 * 64 * (Cin == 16 ? 2 * 4 : 1 * 2);      // 25 taps x NCH 1 x NT x 64 lanes x KPL floats
+      const bool k5w64 = [] { const char* e = getenv("MDF_CONV_K5_WINOGRAD_64"); return e ? atoi(e) != 0 : true; }();   // 0: 32 -> 64 on the direct kernel (read per call)
+      if (use_w2 && !res && Cin == Cin_mem && ((Cin == 32 && Cout == 64 && k5w64) || (Cin == 16 && Cout == 32) || (Cin == 8 && Cout == 16))) {
+        const size_t plain = (size_t)25 * 64 * (Cin == 32 ? 2 * 4 * 4 : (Cin == 16 ? 2 * 4 : 1 * 2));      // 25 taps x NCH x NT x 64 lanes x KPL floats
         const int rc = mdf_wino2d_s2d_dispatch(x, wpack + plain, alpha, beta, y, B, p.Ho, p.Wo, Cin, Cout, relu, stream);
         if (rc != MDF_EUNSUPPORTED) return rc;
       }
