@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include "mdfnet_hip.h"
 
 namespace mdf {
@@ -28,6 +29,12 @@ inline int check_launch(const char* what) {
   if (e != hipSuccess) return fail(MDF_EHIP, "%s: %s", what, hipGetErrorString(e));
   return MDF_OK;
 }
+
+// Development switches (MDF_* environment variables).  A `static const` caller reads its switch once per process; every other
+// caller reads it per call, because tests flip those inside one process.
+inline long long env_int(const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; }   // any integer
+inline long long env_pos(const char* name, long long dflt) { const long long v = env_int(name, 0); return v > 0 ? v : dflt; }   // the value counts only if > 0
+inline bool env_flag(const char* name, bool dflt) { return env_int(name, dflt) != 0; }
 
 // Bijective XCD-aware remap (cdna_hip_programming.md T1): blocks b and b+8 share an XCD, so give
 // every XCD a contiguous chunk of the tile range (neighbouring tiles share source footprints / halos).

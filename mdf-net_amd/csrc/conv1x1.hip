@@ -285,7 +285,7 @@ int launch_1x1(P1& p, hipStream_t st) {
   p.n_runs = (int)runs;
   long long blocks = (runs + 3) / 4;
   int cap = 256 * 8;
-  if (const char* e = getenv("MDF_CONV1X1_BLOCKS")) { if (atoi(e) > 0) cap = atoi(e); }   // dev A/B
+  cap = mdf::env_pos("MDF_CONV1X1_BLOCKS", cap);   // dev A/B
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL((conv1x1_kernel<CIN, COUT>), dim3((unsigned)blocks), dim3(256), 0, st, p);
   return mdf::check_launch("conv1x1_kernel");
@@ -300,7 +300,7 @@ int launch_1x1(P1& p, hipStream_t st) {
 
 int mdf_conv1x1_dispatch(const float* x, const float* wpack, const float* alpha, const float* beta, const float* res, float res_scale,
                          const float* res_up, float* y, int B, int H, int W, int Cin, int Cout, int relu, void* stream) {
-  if (const char* e = getenv("MDF_CONV1X1")) { if (atoi(e) == 0) return MDF_EUNSUPPORTED; }   // A/B and parity-test switch (read per call)
+  if (!mdf::env_flag("MDF_CONV1X1", true)) return MDF_EUNSUPPORTED;   // A/B and parity-test switch (read per call)
   P1 p{};
   p.x = x; p.wpack = wpack; p.alpha = alpha; p.beta = beta; p.res = res; p.res_up = res_up; p.y = y;
   p.res_scale = res_scale; p.relu = relu; p.Ho = H; p.Wo = W; p.npx = (long long)B * H * W;

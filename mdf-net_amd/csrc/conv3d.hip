@@ -21,6 +21,7 @@
 // so no MFMA is spent on structurally-zero taps.
 #include <cstdlib>
 #include "common.h"
+#include "conv_pack.h"
 
 namespace {
 
@@ -505,10 +506,8 @@ __global__ __launch_bounds__(WL ? WL * 64 : 256) void convtr_all_kernel(const Co
   }
   // The fragments of PG positions are requested together and zeroed where they are used (one round trip per group instead of one per
   // position: a persistent wave's tiles run back to back, nobody else hides them)
-#ifndef MDF_CONVTR_PG64
-#define MDF_CONVTR_PG64 0      // dev A/B (build_variant.sh): 1 = the one-tile 64 -> 32 kernels fetch four positions at a time too (measured: @12x37x50 49.9 -> 60.0 us, worse)
-#endif
-  constexpr int PG = (WL != 0 || (CIN >= 64 && MDF_CONVTR_PG64)) ? ((64 / (NCH * MT * KPL) >= 8) ? 8 : (64 / (NCH * MT * KPL) >= 4) ? 4 : 1) : 1;
+  // (the one-tile 64 -> 32 kernels fetching four positions at a time too was measured: @12x37x50 49.9 -> 60.0 us, worse)
+  constexpr int PG = (WL != 0) ? ((64 / (NCH * MT * KPL) >= 8) ? 8 : (64 / (NCH * MT * KPL) >= 4) ? 4 : 1) : 1;
   Frag<KPL> bfa[PG][NCH][MT];
 #pragma unroll
   for (int pos = 0; pos < 8; ++pos) {
@@ -808,10 +807,6 @@ struct WSrc {
 };
 
 // plain: wpack[tap][chunk][nt][q][n][s] = W(cout = nt*16+n, cin = chunk*CK + KPL*q + s, tap)
-__device__ __forceinline__ int pack_plain_total(int Cin, int Cout, int ntaps) {
-  const int KPL = (Cin >= 16) ? 4 : (Cin == 8 ? 2 : 1), CK = 4 * KPL, NCH = Cin / CK, NT = (Cout + 15) / 16;
-  return ntaps * NCH * NT * 64 * KPL;
-}
 __device__ __forceinline__ float pack_plain_elem(const WSrc& src, int i, int Cin, int Cin_mem, int Cout) {
   const int KPL = (Cin >= 16) ? 4 : (Cin == 8 ? 2 : 1), CK = 4 * KPL, NCH = Cin / CK, NT = (Cout + 15) / 16;
   int r = i;
@@ -828,10 +823,6 @@ __device__ __forceinline__ float pack_plain_elem(const WSrc& src, int i, int Cin
 // w-phase packing for Cout < 16 (conv_lds.hip, Cfg::RW): the conv rewritten with GEMM row r*Cout + c = channel c of output
 // phase r (RW phases along w) and KW' = KHW + RW - 1 taps along w; tap kw' of phase r is the original tap kw' - r.
 // wp[tap' = kdh*KW' + kw'][chunk][q][n][s], one n-tile.
-__device__ __forceinline__ int pack_rw_total(int Cin, int nkdh, int KHW, int RW) {
-  const int KPL = (Cin >= 16) ? 4 : (Cin == 8 ? 2 : 1), CK = 4 * KPL, NCH = Cin / CK, KW = KHW + RW - 1;
-  return nkdh * KW * NCH * 64 * KPL;
-}
 __device__ __forceinline__ float pack_rw_elem(const WSrc& src, int i, int Cin, int Cin_mem, int Cout, int KHW, int RW) {
   const int KPL = (Cin >= 16) ? 4 : (Cin == 8 ? 2 : 1), CK = 4 * KPL, NCH = Cin / CK, KW = KHW + RW - 1;
   int r = i;
@@ -847,7 +838,6 @@ __device__ __forceinline__ float pack_rw_elem(const WSrc& src, int i, int Cin, i
 
 // Winograd F(2x2,3x3) weights for conv_lds.hip step_wino: U[kd][a][b] = G g[kd] G^T, G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1];
 // fragments in the order the kernel walks them: [kd][chunk][ab = a*4+b][nt][lane = q*16+m][s], cout = nt*16+m, cin = chunk*16+4q+s.
-__device__ __forceinline__ int pack_wino_total(int Cin, int Cout, int nkd) { return nkd * (Cin / 16) * 16 * ((Cout + 15) / 16) * 64 * 4; }
 __device__ __forceinline__ float pack_wino_elem(const WSrc& src, int i, int Cin, int Cout, int nkd) {
   const int NCH = Cin / 16, NT = (Cout + 15) / 16;
   const float G[4][3] = {{1.f, 0.f, 0.f}, {.5f, .5f, .5f}, {.5f, -.5f, .5f}, {0.f, 0.f, 1.f}};
@@ -894,10 +884,6 @@ __device__ __forceinline__ float pack_wd_elem(const WSrc& src, int i, int Cin) {
 
 // ConvTranspose3d weights [Cin][Cout][3][3][3] -> wpack[tap' = (kd*3+kh)*2+ow][chunk][nt][q][n][s] with GEMM row
 // r = nt*16+n = pw*Cout + cout and kernel tap kw(pw, ow): (0,0)->1, (1,0)->2, (1,1)->0, (0,1)-> structurally zero.
-__device__ __forceinline__ int pack_tr_total(int Cin, int Cout) {
-  const int KPL = (Cin >= 16) ? 4 : 2, CK = 4 * KPL, NCH = Cin / CK, NT = (2 * Cout + 15) / 16;
-  return 18 * NCH * NT * 64 * KPL;
-}
 __device__ __forceinline__ float pack_tr_elem(const WSrc& src, int i, int Cin, int Cout) {
   const int KPL = (Cin >= 16) ? 4 : 2, CK = 4 * KPL, NCH = Cin / CK, NT = (2 * Cout + 15) / 16;
   int r = i;
@@ -915,70 +901,38 @@ __device__ __forceinline__ float pack_tr_elem(const WSrc& src, int i, int Cin, i
   return kw >= 0 ? src.at(cout, cin, (kd * 3 + kh) * 3 + kw) : 0.f;
 }
 
-__host__ __device__ inline int rw_of(int Cout) { return Cout == 8 ? 2 : (Cout == 4 ? 4 : 0); }   // w-phase factor of a stride-1 k3 layer (0 = none)
-__host__ __device__ inline bool wino_built(int Cin, int Cout) {   // 3-D ((16, 32): the input-gradient conv of the stage-0 regulariser's first layer, training)
-  return ((Cout == 16 || Cout == 32) && (Cin == 16 || Cin == 32)) || (Cin == 16 && Cout == 8);
-}
-__host__ __device__ inline bool wino2d_built(int Cin, int Cout) {   // ((16, 32), (32, 64): input gradients of the k5-s2 layers as 3x3 convs over the parity classes, training)
-  return (Cin == 16 && Cout == 16) || (Cin == 32 && Cout == 32) || (Cin == 64 && Cout == 64) || (Cin == 16 && Cout == 32) || (Cin == 32 && Cout == 64);
-}
-__host__ __device__ inline bool wd_built(int Cin, int Cout) { return Cout == 8 && (Cin == 8 || Cin == 16); }   // 3-D, depth-pair Winograd
-// 2-D k5 s2 layers that also run as a Winograd 3x3 conv over the four parity images of their input (conv_lds.hip, LdsConvParams::s2d)
-__host__ __device__ inline bool k5w_built(int Cin, int Cout) { return (Cin == 32 && Cout == 64) || (Cin == 16 && Cout == 32) || (Cin == 8 && Cout == 16); }
-__host__ __device__ inline int padded_cin(int c) { return c <= 4 ? 4 : c; }
+using mdf::padded_cin, mdf::rw_of, mdf::PackLayout, mdf::pack_layout;
 
-// One complete packed weight set, as mdf_conv3d_pack_weights / mdf_conv_pack_weights lay it out: the plain fragments, then
-// (Cout 8 / 4, 3x3 taps) the w-phase fragments, then (where a Winograd kernel exists) the transform-domain fragments, then (3-D,
-// Cout 8) the depth-pair Winograd fragments; or the transposed-conv fragments alone.
+// One complete packed weight set (conv_pack.h has its layout: the segment lengths of every packing above)
 struct PackJob {
   const float* src;
   float* dst;
   int mode, transposed, is3d, Cin_mem, Cout, ntaps, a0, a1;
   int blk0, nblk;
 };
-__host__ __device__ inline void pack_segments(int is3d, int transposed, int Cin_mem, int Cout, int ntaps, long long* plain, long long* rw, long long* wino,
-                                              long long* wd) {
-  const int Cin = padded_cin(Cin_mem);
-  const int KPL = (Cin >= 16) ? 4 : (Cin == 8 ? 2 : 1), NCH = Cin / (4 * KPL);
-  *rw = 0; *wino = 0; *wd = 0;
-  if (transposed) {
-    const int K2 = (Cin >= 16) ? 4 : 2;
-    *plain = 18ll * (Cin / (4 * K2)) * ((2 * Cout + 15) / 16) * 64 * K2;
-    return;
-  }
-  *plain = (long long)ntaps * NCH * ((Cout + 15) / 16) * 64 * KPL;
-  const bool k3 = is3d ? (ntaps == 27) : (ntaps == 9);
-  if (k3 && rw_of(Cout)) *rw = (long long)(is3d ? 9 : 3) * (3 + rw_of(Cout) - 1) * NCH * 64 * KPL;
-  if (k3 && (is3d ? wino_built(Cin_mem, Cout) : wino2d_built(Cin_mem, Cout))) *wino = (long long)(is3d ? 3 : 1) * (Cin / 16) * 16 * ((Cout + 15) / 16) * 64 * 4;
-  if (k3 && is3d && wd_built(Cin_mem, Cout)) *wd = 4ll * NCH * 16 * 64 * KPL;
-  if (!is3d && ntaps == 25 && k5w_built(Cin_mem, Cout)) *wino = (long long)(4 * Cin / 16) * 16 * ((Cout + 15) / 16) * 64 * 4;   // (its only extra segment)
-}
 __device__ __forceinline__ void pack_job_elem(const PackJob& j, long long i) {
   const int Cin = padded_cin(j.Cin_mem);
   WSrc src{j.src, j.transposed ? kSrcSwap : j.mode, j.Cout, j.Cin_mem, j.ntaps, j.a0, j.a1};
-  long long plain, rw, wino, wd;
-  pack_segments(j.is3d, j.transposed, j.Cin_mem, j.Cout, j.ntaps, &plain, &rw, &wino, &wd);
-  if (i >= plain + rw + wino + wd) return;
+  const PackLayout L = pack_layout(j.is3d, j.transposed, j.Cin_mem, j.Cout, j.ntaps);
+  if (i >= L.total()) return;
   float v;
   if (j.transposed) v = pack_tr_elem(src, (int)i, Cin, j.Cout);
-  else if (i < plain) v = pack_plain_elem(src, (int)i, Cin, j.Cin_mem, j.Cout);
-  else if (i < plain + rw) v = pack_rw_elem(src, (int)(i - plain), Cin, j.Cin_mem, j.Cout, 3, rw_of(j.Cout));
-  else if (i < plain + rw + wino) {
+  else if (i < L.rw_off()) v = pack_plain_elem(src, (int)i, Cin, j.Cin_mem, j.Cout);
+  else if (i < L.wino_off()) v = pack_rw_elem(src, (int)(i - L.rw_off()), Cin, j.Cin_mem, j.Cout, 3, rw_of(j.Cout));
+  else if (i < L.wd_off()) {
     if (!j.is3d && j.ntaps == 25) {   // k5 s2 as 3x3 over the parity images: 4*Cin logical input channels
       const WSrc ph{j.src, kSrcK5S2Phases, j.Cout, 4 * j.Cin_mem, 9, j.Cin_mem, 0};
-      v = (j.mode == kSrcDirect) ? pack_wino_elem(ph, (int)(i - plain - rw), 4 * Cin, j.Cout, 1) : 0.f;
+      v = (j.mode == kSrcDirect) ? pack_wino_elem(ph, (int)(i - L.wino_off()), 4 * Cin, j.Cout, 1) : 0.f;
     } else {
-      v = pack_wino_elem(src, (int)(i - plain - rw), Cin, j.Cout, j.is3d ? 3 : 1);
+      v = pack_wino_elem(src, (int)(i - L.wino_off()), Cin, j.Cout, j.is3d ? 3 : 1);
     }
   }
-  else v = pack_wd_elem(src, (int)(i - plain - rw - wino), Cin);
+  else v = pack_wd_elem(src, (int)(i - L.wd_off()), Cin);
   j.dst[i] = v;
 }
 
 __global__ void pack_weights_kernel(PackJob j) {
-  long long plain, rw, wino, wd;
-  pack_segments(j.is3d, j.transposed, j.Cin_mem, j.Cout, j.ntaps, &plain, &rw, &wino, &wd);
-  const long long total = plain + rw + wino + wd;
+  const long long total = pack_layout(j.is3d, j.transposed, j.Cin_mem, j.Cout, j.ntaps).total();
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) pack_job_elem(j, i);
 }
 
@@ -1116,11 +1070,8 @@ __global__ __launch_bounds__(1024) void conv3d_wlds_kernel(const ConvParams p) {
     };
     // groups of RB rows (kd, kh) of three taps; the next group's B fragments are requested before the current group's MFMAs (two register
     // sets).  (8 input channels, 2 registers per fragment: a whole kd plane of 9 taps per group was measured -- 8->16 s2 @24x296x400
-    // 44.7 -> 50.0 us, @8x592x800 58.7 -> 64.8: worse; dev: -DMDF_WLDS_RB8=3)
-#ifndef MDF_WLDS_RB8
-#define MDF_WLDS_RB8 1
-#endif
-    constexpr int RB = (CIN == 8) ? MDF_WLDS_RB8 : 1;
+    // 44.7 -> 50.0 us, @8x592x800 58.7 -> 64.8: worse)
+    constexpr int RB = 1;
     struct RowRegs { Frag<KPL> b[3 * RB][NCH][MT]; };
     auto load_row = [&](int r, RowRegs& rr) {
 #pragma unroll
@@ -1263,11 +1214,11 @@ int launch_conv_mt(ConvParams& p, hipStream_t st) {
   if (MODE == kS2 && CIN == 8 && ST == 0 && tiles_big >= 1024) return launch_conv<CIN, COUT, MODE, 2, 1, ST>(p, st);
   {   // dev A/B: two m-tiles per wave for the mid-size one-tile layers (half the weight bytes through L1 per voxel)
     // (r05: 16 -> 32 stride 2 at 48x148x200 -- 693 four-tile blocks' worth -- 68.6 -> 62.6 us; below ~500 the grid is too small)
-    const long long mt2_min = [] { const char* e = getenv("MDF_CONV3D_MT2_MIN_TILES"); return e ? atoll(e) : 512LL; }();
+    const long long mt2_min = mdf::env_int("MDF_CONV3D_MT2_MIN_TILES", 512);
     if (ST == 0 && MODE != kTr && mt2_min >= 0 && tiles_big < 1024 && tiles_big >= mt2_min && !(CIN >= 32 && p.m_total / 16 < 4096))
       return launch_conv<CIN, COUT, MODE, 2, 1, ST>(p, st);
   }
-  const long long mt_min = [] { const char* e = getenv("MDF_CONV3D_MT_MIN_TILES"); return e ? atoll(e) : 1024LL; }();   // dev A/B (read per call)
+  const long long mt_min = mdf::env_int("MDF_CONV3D_MT_MIN_TILES", 1024);   // dev A/B (read per call)
   if (tiles_big >= mt_min) return launch_conv<CIN, COUT, MODE, MTMAX, 1, ST>(p, st);
   // few tiles and a deep K (27*CIN >= 864): split the taps over the block's waves
   const long long tiles_1 = p.m_total / 16 * (MODE == kTr ? 4 : 1);
@@ -1276,7 +1227,7 @@ int launch_conv_mt(ConvParams& p, hipStream_t st) {
     // L1 for 16 voxels -- 1388 blocks x 442 KB = 0.6 GB from the L2s per launch at 12x37x50; two tiles halve that
     // (r05, 64 output channels at ~1400 tiles: 64 -> 64 @12x37x50 62 -> 57 us, 32 -> 64 s2 @24x74x100 35 -> 31; the 32 -> 32 layers and
     //  the volumes under ~500 tiles are indifferent or lose: they keep one tile)
-    const int sk_mt = [] { const char* e = getenv("MDF_CONV3D_SK_MT"); return e ? atoi(e) : 0; }();   // dev A/B (read per call): 0 = the rule
+    const int sk_mt = mdf::env_int("MDF_CONV3D_SK_MT", 0);   // dev A/B (read per call): 0 = the rule
     if (ST == 0 && (sk_mt == 2 || (sk_mt == 0 && COUT >= 64)) && tiles_1 >= 1024) return launch_conv<CIN, COUT, MODE, 2, 4, ST>(p, st);
     return launch_conv<CIN, COUT, MODE, 1, 4, ST>(p, st);
   }
@@ -1285,11 +1236,7 @@ int launch_conv_mt(ConvParams& p, hipStream_t st) {
 
 }  // namespace
 
-static int64_t pack_total(int is3d, int transposed, int Cin_mem, int Cout, int ntaps) {
-  long long plain, rw, wino, wd;
-  pack_segments(is3d, transposed, Cin_mem, Cout, ntaps, &plain, &rw, &wino, &wd);
-  return plain + rw + wino + wd;
-}
+static int64_t pack_total(int is3d, int transposed, int Cin_mem, int Cout, int ntaps) { return pack_layout(is3d, transposed, Cin_mem, Cout, ntaps).total(); }
 
 extern "C" int64_t mdf_conv3d_packed_size(int Cin, int Cout) {
   if (Cin < 8 || Cout < 1) return 0;
@@ -1425,25 +1372,22 @@ static int conv3d_entry(const float* x, const float* wpack, const float* alpha, 
   p.B = B; p.Di = Di; p.Hi = Hi; p.Wi = Wi; p.relu = relu;
   if (stat) { p.stat_mode = stat->mode; p.stat_y = stat->y; p.stat_aux = stat->aux; p.stat_out = stat->out; p.stat_slices = stat->nslices; }
   const int m = transposed ? kTr : (stride == 2 ? kS2 : kS1);
-  p.kd_skip = [] { const char* e = getenv("MDF_CONV3D_KDSKIP"); return e ? atoi(e) : 1; }() && Di <= 3;   // dev A/B (read per call)
+  p.kd_skip = mdf::env_int("MDF_CONV3D_KDSKIP", 1) && Di <= 3;   // dev A/B (read per call)
   if (m == kS1) { p.Do = Di; p.Ho = Hi; p.Wo = Wi; }
   else if (m == kS2) { p.Do = (Di - 1) / 2 + 1; p.Ho = (Hi - 1) / 2 + 1; p.Wo = (Wi - 1) / 2 + 1; }
   else { p.Do = 2 * Di; p.Ho = 2 * Hi; p.Wo = 2 * Wi; }
   p.m_total = (m == kTr) ? (long long)B * Di * Hi * Wi : (long long)B * p.Do * p.Ho * p.Wo;
-  const long long lds_min = [] {  // test hook (read per call): MDF_CONV_LDS_MIN_VOXELS=0 forces the LDS kernels at any size
-    const char* e = getenv("MDF_CONV_LDS_MIN_VOXELS");
-    return e ? atoll(e) : 150000LL;
-  }();
+  const long long lds_min = mdf::env_int("MDF_CONV_LDS_MIN_VOXELS", 150000);   // test hook (read per call): 0 forces the LDS kernels at any size
   if (m == kS1 && p.m_total >= lds_min) {  // large stride-1 layers: LDS-staged planes (conv_lds.hip)
     const int rc = mdf_conv_lds_dispatch(x, wpack, alpha, beta, res, 1.0f, nullptr, y, B, Di, Hi, Wi, Cin, Cin, Cout, 3, 3, 1, relu, stream, 0, 0, stat);
     if (rc != MDF_EUNSUPPORTED) return rc;
   }
   if (m == kTr && !stat) {   // large transposed layers: all four parity classes per tile (convtr_all_kernel)
-    const long long tr_min = [] { const char* e = getenv("MDF_CONVTR_ALL_MIN_VOXELS"); return e ? atoll(e) : 40000LL; }();   // dev A/B (read per call); -1 = never  (r05: 100000 -> 40000, 32->16 @2x148x200 36.7 -> 30.2 us, @6x74x100 29.2 -> 24.7)
-    const int ns = [] { const char* e = getenv("MDF_CONVTR_NS"); return e ? atoi(e) : 0; }();   // dev A/B and the equality test (read per call): 0 = the rule, 1 = off
+    const long long tr_min = mdf::env_int("MDF_CONVTR_ALL_MIN_VOXELS", 40000);   // dev A/B (read per call); -1 = never  (r05: 100000 -> 40000, 32->16 @2x148x200 36.7 -> 30.2 us, @6x74x100 29.2 -> 24.7)
+    const int ns = mdf::env_int("MDF_CONVTR_NS", 0);   // dev A/B and the equality test (read per call): 0 = the rule, 1 = off
     // one class per persistent block with the class's slots in LDS (convtr_cls_kernel; r05: @12x37x50 42.6 -> 32.9 us, @3x37x50 19.0 -> 14.4;
     // a single-plane volume halves the work of the pd = 1 classes and with it the block shares: @1x74x100 15.3 -> 16.6, so that one stays)
-    const int tcl = [] { const char* e = getenv("MDF_CONVTR_CLS"); return e ? atoi(e) : -1; }();   // dev A/B and the equality test (read per call): 0 = off
+    const int tcl = mdf::env_int("MDF_CONVTR_CLS", -1);   // dev A/B and the equality test (read per call): 0 = off
     if (tr_min >= 0 && Cin == 64 && Cout == 32 && ns == 0) {
       if (tcl == 1) return launch_convtr_cls<64, 32, 12, 4>(p, (hipStream_t)stream);
       if (tcl == 2 || (tcl < 0 && Di >= 2)) return launch_convtr_cls<64, 32, 16, 2>(p, (hipStream_t)stream);
@@ -1452,15 +1396,12 @@ static int conv3d_entry(const float* x, const float* wpack, const float* alpha, 
       // One 16-voxel m-tile per wave (r05; two until then): these layers' time is MFMA time PLUS streaming time (skip + output), and the
       // smaller accumulator set lets 4-5 waves per SIMD instead of 3-4 overlap one block's streaming with another's MFMAs:
       // 32->16 @24x74x100 89.2 -> 69.3 us, 16->8 @12x148x200 51.2 -> 47.4, @4x296x400 79.4 -> 74.7 (four tiles: 88 / 67 / 97)
-      const int mt = [] { const char* e = getenv("MDF_CONVTR_MT"); return e ? atoi(e) : 1; }();   // dev A/B (read per call)
       // LDS-weights persistent form (r05): 32->16 @24x74x100 69.5 -> 60.8 us, @2x148x200 29.9 -> 26.1, @6x74x100 24.2 -> 21.3; 16->8 @12x148x200 47.6 -> 44.9, @4x296x400 71.0 -> 59.3
-      const int twl = [] { const char* e = getenv("MDF_CONVTR_WLDS"); return e ? atoi(e) : 1; }();   // dev A/B and the equality test (read per call): 0 = off, 2 = fewer waves / two m-tiles
+      const int twl = mdf::env_int("MDF_CONVTR_WLDS", 1);   // dev A/B and the equality test (read per call): 0 = off, 2 = fewer waves / two m-tiles
       if (Cin == 16 && Cout == 8 && twl == 1) return launch_convtr_all_wl<16, 8, 1, 16>(p, (hipStream_t)stream);
       if (Cin == 16 && Cout == 8 && twl == 2) return launch_convtr_all_wl<16, 8, 2, 12>(p, (hipStream_t)stream);
       if (Cin == 32 && Cout == 16 && twl == 1) return launch_convtr_all_wl<32, 16, 1, 12>(p, (hipStream_t)stream);
       if (Cin == 32 && Cout == 16 && twl == 2) return launch_convtr_all_wl<32, 16, 1, 8>(p, (hipStream_t)stream);
-      if (Cin == 16 && Cout == 8 && mt == 2) return launch_convtr_all<16, 8, 2>(p, (hipStream_t)stream);
-      if (Cin == 32 && Cout == 16 && mt == 2) return launch_convtr_all<32, 16, 2>(p, (hipStream_t)stream);
       if (Cin == 16 && Cout == 8) return launch_convtr_all<16, 8, 1>(p, (hipStream_t)stream);
       if (Cin == 32 && Cout == 16) return launch_convtr_all<32, 16, 1>(p, (hipStream_t)stream);
       if (Cin == 64 && Cout == 32) return launch_convtr_all<64, 32, 1>(p, (hipStream_t)stream);
@@ -1475,7 +1416,7 @@ static int conv3d_entry(const float* x, const float* wpack, const float* alpha, 
   }
   // weights-in-LDS form for the small and mid-size layers whose packed set fits (eval)
   if (stat) {    // training: the same form with the epilogue sums
-    const int wlt = [] { const char* e = getenv("MDF_CONV3D_WLDS_TRAIN"); return e ? atoi(e) : 1; }();   // dev A/B (read per call): 0 = off
+    const int wlt = mdf::env_int("MDF_CONV3D_WLDS_TRAIN", 1);   // dev A/B (read per call): 0 = off
     if (wlt == 1) {
       if (Cin == 32 && Cout == 32 && m == kS1) return launch_conv_wlds<32, 32, kS1, 1, 1>(p, (hipStream_t)stream);
       if (Cin == 16 && Cout == 16 && m == kS1) return launch_conv_wlds<16, 16, kS1, 1, 1>(p, (hipStream_t)stream);
@@ -1484,18 +1425,14 @@ static int conv3d_entry(const float* x, const float* wpack, const float* alpha, 
     }
   }
   if (!stat) {
-    const int wl = [] { const char* e = getenv("MDF_CONV3D_WLDS"); return e ? atoi(e) : 1; }();   // dev A/B (read per call): 0 = off
+    const int wl = mdf::env_int("MDF_CONV3D_WLDS", 1);   // dev A/B (read per call): 0 = off
     if (wl == 1) {     // (two m-tiles per wave were measured and lose: 32 -> 32 @6x74x100 35 -> 64 us, 16 -> 32 s2 @48x148x200 61 -> 76)
       if (Cin == 32 && Cout == 32 && m == kS1) return launch_conv_wlds<32, 32, kS1, 1>(p, (hipStream_t)stream);
       if (Cin == 16 && Cout == 32 && m == kS2) return launch_conv_wlds<16, 32, kS2, 1>(p, (hipStream_t)stream);
     }
-    const int wl8 = [] { const char* e = getenv("MDF_CONV3D_WLDS8"); return e ? atoi(e) : 2; }();   // dev A/B (read per call): m-tiles per wave, 0 = off
+    const bool wl8 = mdf::env_flag("MDF_CONV3D_WLDS8", true);   // dev A/B and the equality test (read per call): 0 = off
     // (8 -> 16 stride 2, the gather-heavy layers: @24x296x400 50.4 us -> 46.5 / 43.5 / 49.7 with 1 / 2 / 4 m-tiles per wave, @8x592x800 66.0 -> 60.1 / 55.0 / 64.8)
-    if (Cin == 8 && Cout == 16 && m == kS2) {
-      if (wl8 == 1) return launch_conv_wlds<8, 16, kS2, 1>(p, (hipStream_t)stream);
-      if (wl8 == 2) return launch_conv_wlds<8, 16, kS2, 2>(p, (hipStream_t)stream);
-      if (wl8 == 4) return launch_conv_wlds<8, 16, kS2, 4>(p, (hipStream_t)stream);
-    }
+    if (wl8 && Cin == 8 && Cout == 16 && m == kS2) return launch_conv_wlds<8, 16, kS2, 2>(p, (hipStream_t)stream);
   }
   // stride 1 (every Cin x Cout the nets use)
   MDF_CONV_CASE(32, 16, kS1) MDF_CONV_CASE(16, 16, kS1) MDF_CONV_CASE(32, 32, kS1) MDF_CONV_CASE(64, 64, kS1)

@@ -16,6 +16,7 @@
 #include <mutex>
 #include <type_traits>
 #include "common.h"
+#include "conv_pack.h"
 
 #include "conv_lds_common.h"
 
@@ -779,7 +780,7 @@ int launch_lds(LdsConvParams& p, hipStream_t st) {
     // (one resident block and long pair steps: 179 -> 172 us on 16->8 @24x296x400 with 3; the three-plane ring form of that layer,
     //  two resident blocks: 163 us with 6, 158 with 4, 151 with 2)
     long long ipb = C::STREAM ? 2 : ((C::RD == 2 && blocks_per_cu == 1) ? 3 : 6);
-    if (const char* e = getenv("MDF_CONV_ITEMS_PER_BLOCK")) { if (atoi(e) > 0) ipb = atoi(e); }   // dev A/B
+    ipb = mdf::env_pos("MDF_CONV_ITEMS_PER_BLOCK", ipb);   // dev A/B
     long long want = (ipb * max_grid + tiles - 1) / tiles;
     if (want < 1) want = 1;
     if (want > p.D / 3) want = p.D / 3;
@@ -803,7 +804,7 @@ int launch_lds(LdsConvParams& p, hipStream_t st) {
         }
       }
     }
-    if (const char* e = getenv("MDF_CONV_DCH")) { if (atoi(e) > 0) dch = atoi(e); }   // dev A/B
+    dch = mdf::env_pos("MDF_CONV_DCH", dch);   // dev A/B
     if (C::RD == 2 && (dch & 1)) ++dch;   // depth-pair form: whole pairs per chunk (an odd tail pair computes a plane it does not store)
     p.dch = dch;
     p.dchunks = (p.D + dch - 1) / dch;
@@ -816,7 +817,7 @@ int launch_lds(LdsConvParams& p, hipStream_t st) {
     p.n_tiles = (int)tiles;
     p.tiles_per_item = 0;
     long long tpb = 2;   // small layers: residency (4 blocks/CU) beats long runs -- 30 -> 20 us on the refine-size convs (A/B)
-    if (const char* e = getenv("MDF_CONV2D_TILES_PER_BLOCK")) { if (atoi(e) > 0) tpb = atoi(e); }   // dev A/B
+    tpb = mdf::env_pos("MDF_CONV2D_TILES_PER_BLOCK", tpb);   // dev A/B
     long long g = tiles / tpb;                   // >= tpb tiles per block
     if (g < 256) g = 256;
     if (g > max_grid) g = max_grid;
@@ -837,7 +838,7 @@ int launch_lds(LdsConvParams& p, hipStream_t st) {
     attr_done = true;
   }
   int grid = max_grid;
-  if (const char* g = getenv("MDF_CONV_GRID")) { if (atoi(g) > 0) grid = atoi(g); }   // dev: residency experiments
+  grid = mdf::env_pos("MDF_CONV_GRID", grid);   // dev: residency experiments
   if (grid > p.n_items) grid = p.n_items;
   if (ST) {
     if (KD == 1) {   // groups x blocks-per-group
@@ -855,11 +856,18 @@ int launch_lds(LdsConvParams& p, hipStream_t st) {
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv_lds_kernel<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, ST>, 256, kLds);
     hipFuncAttributes fa{};
     (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&conv_lds_kernel<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, ST>));
-    fprintf(stderr, "[conv_lds<%d,%d,%d,%d,%d,%d,%d,rw%d>] LDS %zu B dyn + %zu static, regs %d, occupancy API: %d blocks/CU (%s), grid %d, items %d\n",
-            CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, kLds, fa.sharedSizeBytes, fa.numRegs, nb, hipGetErrorString(e), grid, p.n_items);
+    fprintf(stderr, "[conv_lds<%d,%d,%d,%d,%d,%d,%d,rw%d wg%d st%d>] LDS %zu B dyn + %zu static, regs %d, occupancy API: %d blocks/CU (%s), grid %d, items %d\n",
+            CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, ST, kLds, fa.sharedSizeBytes, fa.numRegs, nb, hipGetErrorString(e), grid, p.n_items);
   }
   hipLaunchKernelGGL((conv_lds_kernel<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, ST>), dim3(grid), dim3(256), kLds, st, p);
   return mdf::check_launch("conv_lds_kernel");
+}
+
+// the training-capable cases: the eval kernel, or the one with the epilogue sums of stat->mode (1 or 2)
+template <int CIN, int CIN_MEM, int COUT, int KD, int KHW, int SHW, int MT, int RW = 1, int WG = 0>
+int launch_lds_stat(LdsConvParams& p, hipStream_t st, const mdf::ConvStat* stat) {
+  if (!stat) return launch_lds<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, 0>(p, st);
+  return stat->mode == 1 ? launch_lds<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, 1>(p, st) : launch_lds<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, 2>(p, st);
 }
 
 }  // namespace
@@ -884,7 +892,7 @@ extern "C" int mdf_debug_read_stamps(unsigned long long* out8, int reset) {
 // layers the training step runs raw with epilogue sums (forward statistics / backward reductions): both variants
 #define LDS_CASE_T(ci, cim, co, kd, k, s, mt)                                                    \
   if (Cin == ci && Cin_mem == cim && Cout == co && KD == kd && KHW == k && stride == s)          \
-    return !stat ? launch_lds<ci, cim, co, kd, k, s, mt>(p, (hipStream_t)stream) : (stat->mode == 1 ? launch_lds<ci, cim, co, kd, k, s, mt, 1, 0, 1>(p, (hipStream_t)stream) : launch_lds<ci, cim, co, kd, k, s, mt, 1, 0, 2>(p, (hipStream_t)stream));
+    return launch_lds_stat<ci, cim, co, kd, k, s, mt>(p, (hipStream_t)stream, stat);
 
 // stream -> scheduler slot (launches on one stream are ordered, so they can share a slot; different streams must not).
 // A slot stays bound to its stream handle until mdf_release_stream(stream) gives it back (long-lived processes that
@@ -913,36 +921,38 @@ extern "C" int mdf_release_stream(void* stream) {
   return MDF_OK;   // never used by a conv launch: nothing to release
 }
 
-// w-phase variants read the expanded packing that conv3d.hip appends after the plain one (mdf_conv_rw_of / pack functions)
-#define LDS_CASE_RW(ci, cim, co, kd, k, s, mt, rw)                                               \
-  if (!stat && use_rw && Cin == ci && Cin_mem == cim && Cout == co && KD == kd && KHW == k && stride == s && !res_up) { \
-    p.wpack = wpack + (size_t)kd * k * k * ci * 16;                                              \
-    return launch_lds<ci, cim, co, kd, k, s, mt, rw>(p, (hipStream_t)stream);                    \
+// The forms below read a segment behind the plain fragments; conv_pack.h says where it lies and which sets carry it.  A case whose
+// set has no such segment does not launch (the dispatch goes on to the next form).
+// w-phase variants
+#define LDS_CASE_RW(ci, cim, co, kd, k, s, mt, nrw)                                              \
+  if (!stat && use_rw && Cin == ci && Cin_mem == cim && Cout == co && KD == kd && KHW == k && stride == s && !res_up && L.rw > 0) { \
+    p.wpack = wpack + L.rw_off();                                                                \
+    return launch_lds<ci, cim, co, kd, k, s, mt, nrw>(p, (hipStream_t)stream);                   \
   }
-#define LDS_CASE_RW_T(ci, cim, co, kd, k, s, mt, rw)                                             \
-  if (use_rw && Cin == ci && Cin_mem == cim && Cout == co && KD == kd && KHW == k && stride == s && !res_up) { \
-    p.wpack = wpack + (size_t)kd * k * k * ci * 16;                                              \
-    return !stat ? launch_lds<ci, cim, co, kd, k, s, mt, rw>(p, (hipStream_t)stream) : (stat->mode == 1 ? launch_lds<ci, cim, co, kd, k, s, mt, rw, 0, 1>(p, (hipStream_t)stream) : launch_lds<ci, cim, co, kd, k, s, mt, rw, 0, 2>(p, (hipStream_t)stream)); \
+#define LDS_CASE_RW_T(ci, cim, co, kd, k, s, mt, nrw)                                            \
+  if (use_rw && Cin == ci && Cin_mem == cim && Cout == co && KD == kd && KHW == k && stride == s && !res_up && L.rw > 0) { \
+    p.wpack = wpack + L.rw_off();                                                                \
+    return launch_lds_stat<ci, cim, co, kd, k, s, mt, nrw>(p, (hipStream_t)stream, stat);        \
   }
 
-// Winograd variants read the transform-domain weights appended behind the plain (and w-phase) packing
+// Winograd variants: the transform-domain weights
 #define LDS_CASE_WG(ci, co)                                                                      \
-  if (use_wg && KD == 3 && KHW == 3 && stride == 1 && Cin == ci && Cin_mem == ci && Cout == co && !res_up) { \
-    p.wpack = wpack + (size_t)27 * ci * (((co + 15) / 16) * 16) + (co == 8 ? (size_t)36 * ci * 16 : 0); \
-    return !stat ? launch_lds<ci, ci, co, 3, 3, 1, 1, 2, 1>(p, (hipStream_t)stream) : (stat->mode == 1 ? launch_lds<ci, ci, co, 3, 3, 1, 1, 2, 1, 1>(p, (hipStream_t)stream) : launch_lds<ci, ci, co, 3, 3, 1, 1, 2, 1, 2>(p, (hipStream_t)stream)); \
+  if (use_wg && KD == 3 && KHW == 3 && stride == 1 && Cin == ci && Cin_mem == ci && Cout == co && !res_up && L.wino > 0) { \
+    p.wpack = wpack + L.wino_off();                                                              \
+    return launch_lds_stat<ci, ci, co, 3, 3, 1, 1, 2, 1>(p, (hipStream_t)stream, stat);          \
   }
 #define LDS_CASE_WG2(ci, co)                                                                     \
-  if (use_wg && KD == 1 && KHW == 3 && stride == 1 && Cin == ci && Cin_mem == ci && Cout == co && !res_up && (!shuffle2 || (ci == 16 && co == 32) || (ci == 32 && co == 64))) { \
-    p.wpack = wpack + (size_t)9 * ci * (((co + 15) / 16) * 16);                                  \
-    return !stat ? launch_lds<ci, ci, co, 1, 3, 1, 1, 2, 1>(p, (hipStream_t)stream) : (stat->mode == 1 ? launch_lds<ci, ci, co, 1, 3, 1, 1, 2, 1, 1>(p, (hipStream_t)stream) : launch_lds<ci, ci, co, 1, 3, 1, 1, 2, 1, 2>(p, (hipStream_t)stream)); \
+  if (use_wg && KD == 1 && KHW == 3 && stride == 1 && Cin == ci && Cin_mem == ci && Cout == co && !res_up && L.wino > 0 && (!shuffle2 || (ci == 16 && co == 32) || (ci == 32 && co == 64))) { \
+    p.wpack = wpack + L.wino_off();                                                              \
+    return launch_lds_stat<ci, ci, co, 1, 3, 1, 1, 2, 1>(p, (hipStream_t)stream, stat);          \
   }
 
-// depth-pair Winograd (3-D, Cout 8): its fragments follow the plain, w-phase and (Cin 16) Winograd ones
+// depth-pair Winograd (3-D, Cout 8)
 #define LDS_CASE_WD(ci)                                                                          \
-  if (use_wd && KD == 3 && KHW == 3 && stride == 1 && Cin == ci && Cin_mem == ci && Cout == 8 && !res_up && D >= 2) { \
-    p.wpack = wpack + (size_t)27 * ci * 16 + (size_t)36 * ci * 16 + (ci == 16 ? (size_t)3 * 16 * 64 * 4 : 0); \
+  if (use_wd && KD == 3 && KHW == 3 && stride == 1 && Cin == ci && Cin_mem == ci && Cout == 8 && !res_up && D >= 2 && L.wd > 0) { \
+    p.wpack = wpack + L.wd_off();                                                                \
     if (ci == 16 && wd_stream && !stat) return launch_lds<ci, ci, 8, 3, 3, 1, 1, 2, 3>(p, (hipStream_t)stream); \
-    return !stat ? launch_lds<ci, ci, 8, 3, 3, 1, 1, 2, 2>(p, (hipStream_t)stream) : (stat->mode == 1 ? launch_lds<ci, ci, 8, 3, 3, 1, 1, 2, 2, 1>(p, (hipStream_t)stream) : launch_lds<ci, ci, 8, 3, 3, 1, 1, 2, 2, 2>(p, (hipStream_t)stream)); \
+    return launch_lds_stat<ci, ci, 8, 3, 3, 1, 1, 2, 2>(p, (hipStream_t)stream, stat);           \
   }
 
 int mdf_wino3d_dispatch(const float* x, const float* wpack_wino, const float* alpha, const float* beta, const float* res, float res_scale,
@@ -955,10 +965,14 @@ int mdf_wino2d_s2d_dispatch(const float* x, const float* wpack_k5w, const float*
 int mdf_conv_lds_dispatch(const float* x, const float* wpack, const float* alpha, const float* beta, const float* res,
                           float res_scale, const float* res_up, float* y, int B, int D, int H, int W, int Cin, int Cin_mem, int Cout, int KD,
                           int KHW, int stride, int relu, void* stream, int planar_in, int shuffle2, const mdf::ConvStat* stat) {
-  static const int wd_mask = [] { const char* e = getenv("MDF_CONV_WD"); return e ? atoi(e) : 3; }();   // dev A/B: bit 0 Cin 8, bit 1 Cin 16
-  const bool wd_stream = [] { const char* e = getenv("MDF_CONV_WD_STREAM"); return e ? atoi(e) != 0 : true; }();   // dev A/B (read per call): ring of 3 planes
-  static const bool use_wg = [] { const char* e = getenv("MDF_CONV_WINOGRAD"); return e ? atoi(e) != 0 : true; }();   // dev A/B
-  static const bool use_rw = [] { const char* e = getenv("MDF_CONV_RW"); return e ? atoi(e) != 0 : true; }();   // dev A/B
+  static const int wd_mask = mdf::env_int("MDF_CONV_WD", 3);   // dev A/B: bit 0 Cin 8, bit 1 Cin 16
+  const bool wd_stream = mdf::env_flag("MDF_CONV_WD_STREAM", true);   // dev A/B (read per call): ring of 3 planes
+  static const bool use_wg = mdf::env_flag("MDF_CONV_WINOGRAD", true);   // dev A/B
+  static const bool use_rw = mdf::env_flag("MDF_CONV_RW", true);   // dev A/B
+  // dev A/B and the equality tests (read per call): the k5-s2 Winograd forms, wino3d.hip, wino2d.hip, 32 -> 64 k5 s2 on the direct kernel (0)
+  const bool k5w = mdf::env_flag("MDF_CONV_K5_WINOGRAD", true), use_w3 = mdf::env_flag("MDF_CONV_WINO3D", true);
+  const bool use_w2 = mdf::env_flag("MDF_CONV_WINO2D", true), k5w64 = mdf::env_flag("MDF_CONV_K5_WINOGRAD_64", true);
+  const mdf::PackLayout L = mdf::pack_layout(KD == 3, 0, Cin_mem, Cout, KD * KHW * KHW);   // this layer's packed set
   LdsConvParams p{};
   p.x = x; p.wpack = wpack; p.alpha = alpha; p.beta = beta; p.res = res; p.res_scale = res_scale; p.res_up = res_up; p.y = y;
   p.B = B; p.D = D; p.H = H; p.W = W; p.relu = relu; p.planar_in = planar_in; p.shuffle2 = shuffle2;
@@ -969,33 +983,24 @@ int mdf_conv_lds_dispatch(const float* x, const float* wpack, const float* alpha
   }
   p.sched_slot = sched_slot_of(stream);
   if (p.sched_slot < 0) return mdf::fail(MDF_EUNSUPPORTED, "conv kernels support up to %d distinct HIP streams per process", kSchedSlots);
-  {
-    const char* e = getenv("MDF_CONV_PREFETCH_EARLY");   // A/B switch (dev): default = after the MFMA block
-    p.prefetch_early = e ? atoi(e) : 0;
-  }
+  p.prefetch_early = mdf::env_int("MDF_CONV_PREFETCH_EARLY", 0);   // A/B switch (dev, read per call): default = after the MFMA block
   const int pad = (KHW - 1) / 2;
   p.Ho = (H + 2 * pad - KHW) / stride + 1;
   p.Wo = (W + 2 * pad - KHW) / stride + 1;
   // The 2-D k5 s2 layers as a Winograd 3x3 conv over the four parity images of their input (16 -> 32 is 64 -> 32: 16 instead of 25 MFMA groups
   // per input channel, direct 163 -> 141 us; wino2d.hip then skips the groups whose weights are structurally zero, 12.25 per input channel:
-  // 140 -> 114 us, profiles/r07_bench_cfg2.md); the transform-domain fragments follow the 25 plain taps (conv3d.hip: k5w_built).  (8 -> 16
+  // 140 -> 114 us, profiles/r07_bench_cfg2.md); the transform-domain fragments follow the 25 plain taps (conv_pack.h: k5w_built).  (8 -> 16
   // and 32 -> 64 the same way; 32 -> 64 walks its 128 logical channels in two passes over the LDS plane of 64: direct 159 -> 127 us.  32 -> 16 over the parity images, measured 200 against 203 us -- that layer waits on HBM, and
   // one block per CU does not help it.)
-  {
-    const bool k5w = [] { const char* e = getenv("MDF_CONV_K5_WINOGRAD"); return e ? atoi(e) != 0 : true; }();   // dev A/B (read per call)
-    if (use_wg && k5w && KD == 1 && KHW == 5 && stride == 2 && !stat && !res_up && !shuffle2 && !planar_in && H % 2 == 0 && W % 2 == 0) {
-      // (wino2d.hip's S2D form first: pinned accumulators, one transform cluster per chunk -- 16 -> 32 and, there only, 8 -> 16 and 32 -> 64)
-      const bool use_w2 = [] { const char* e = getenv("MDF_CONV_WINO2D"); return e ? atoi(e) != 0 : true; }();
-      const bool k5w64 = [] { const char* e = getenv("MDF_CONV_K5_WINOGRAD_64"); return e ? atoi(e) != 0 : true; }();   // 0: 32 -> 64 on the direct kernel (read per call)
-      if (use_w2 && !res && Cin == Cin_mem && ((Cin == 32 && Cout == 64 && k5w64) || (Cin == 16 && Cout == 32) || (Cin == 8 && Cout == 16))) {
-        const size_t plain = (size_t)25 * 64 * (Cin == 32 ? 2 * 4 * 4 : (Cin == 16 ? 2 * 4 : 1 * 2));      // 25 taps x NCH x NT x 64 lanes x KPL floats
-        const int rc = mdf_wino2d_s2d_dispatch(x, wpack + plain, alpha, beta, y, B, p.Ho, p.Wo, Cin, Cout, relu, stream);
-        if (rc != MDF_EUNSUPPORTED) return rc;
-      }
-      if (Cin == 16 && Cin_mem == 16 && Cout == 32) {
-        p.s2d = 1; p.wpack = wpack + (size_t)25 * 1 * 2 * 64 * 4;
-        return launch_lds<64, 64, 32, 1, 3, 1, 1, 2, 1>(p, (hipStream_t)stream);
-      }
+  if (use_wg && k5w && KD == 1 && KHW == 5 && stride == 2 && !stat && !res_up && !shuffle2 && !planar_in && H % 2 == 0 && W % 2 == 0 && L.wino > 0) {
+    // (wino2d.hip's S2D form first: pinned accumulators, one transform cluster per chunk -- 16 -> 32 and, there only, 8 -> 16 and 32 -> 64)
+    if (use_w2 && !res && Cin == Cin_mem && ((Cin == 32 && Cout == 64 && k5w64) || (Cin == 16 && Cout == 32) || (Cin == 8 && Cout == 16))) {
+      const int rc = mdf_wino2d_s2d_dispatch(x, wpack + L.wino_off(), alpha, beta, y, B, p.Ho, p.Wo, Cin, Cout, relu, stream);
+      if (rc != MDF_EUNSUPPORTED) return rc;
+    }
+    if (Cin == 16 && Cin_mem == 16 && Cout == 32) {
+      p.s2d = 1; p.wpack = wpack + L.wino_off();
+      return launch_lds<64, 64, 32, 1, 3, 1, 1, 2, 1>(p, (hipStream_t)stream);
     }
   }
   if (shuffle2 && Cout == 64 && !use_wg) return mdf::fail(MDF_EUNSUPPORTED, "pixel-shuffle store for Cout = 64 is built into the Winograd form only (MDF_CONV_WINOGRAD=0 is set)");
@@ -1003,20 +1008,14 @@ int mdf_conv_lds_dispatch(const float* x, const float* wpack, const float* alpha
   { const bool use_wd = use_wg && (wd_mask & 1); LDS_CASE_WD(8) }
   { const bool use_wd = use_wg && (wd_mask & 2); LDS_CASE_WD(16) }
   // 3-D stride-1 layers with 16 output channels, eval: input-stationary Winograd (wino3d.hip); same fragments as the form below
-  {
-    const bool use_w3 = [] { const char* e = getenv("MDF_CONV_WINO3D"); return e ? atoi(e) != 0 : true; }();   // dev A/B and the equality test (read per call)
-    if (use_wg && use_w3 && !stat && KD == 3 && KHW == 3 && stride == 1 && Cin == Cin_mem && !res_up && !shuffle2 && Cout % 16 == 0) {
-      const int rc = mdf_wino3d_dispatch(x, wpack + (size_t)27 * Cin * Cout, alpha, beta, res, res_scale, y, B, D, H, W, Cin, Cout, relu, stream);
-      if (rc != MDF_EUNSUPPORTED) return rc;
-    }
+  if (use_wg && use_w3 && !stat && KD == 3 && KHW == 3 && stride == 1 && Cin == Cin_mem && !res_up && !shuffle2 && Cout % 16 == 0 && L.wino > 0) {
+    const int rc = mdf_wino3d_dispatch(x, wpack + L.wino_off(), alpha, beta, res, res_scale, y, B, D, H, W, Cin, Cout, relu, stream);
+    if (rc != MDF_EUNSUPPORTED) return rc;
   }
   // 2-D 3x3 stride-1 layers of the feature pyramid, eval: wino2d.hip (same fragments as LDS_CASE_WG2 below)
-  {
-    const bool use_w2 = [] { const char* e = getenv("MDF_CONV_WINO2D"); return e ? atoi(e) != 0 : true; }();   // dev A/B and the equality test (read per call)
-    if (use_wg && use_w2 && !stat && KD == 1 && KHW == 3 && stride == 1 && Cin == Cin_mem && !res_up && !shuffle2 && !planar_in && D == 1) {
-      const int rc = mdf_wino2d_dispatch(x, wpack + (size_t)9 * Cin * (((Cout + 15) / 16) * 16), alpha, beta, res, res_scale, y, B, H, W, Cin, Cout, relu, stream);
-      if (rc != MDF_EUNSUPPORTED) return rc;
-    }
+  if (use_wg && use_w2 && !stat && KD == 1 && KHW == 3 && stride == 1 && Cin == Cin_mem && !res_up && !shuffle2 && !planar_in && D == 1 && L.wino > 0) {
+    const int rc = mdf_wino2d_dispatch(x, wpack + L.wino_off(), alpha, beta, res, res_scale, y, B, H, W, Cin, Cout, relu, stream);
+    if (rc != MDF_EUNSUPPORTED) return rc;
   }
   // 3-D stride-1 layers with 16 output channels: Winograd F(2x2,3x3) in (h,w)
   LDS_CASE_WG(16, 16) LDS_CASE_WG(32, 16) LDS_CASE_WG(32, 32) LDS_CASE_WG(16, 8) LDS_CASE_WG(16, 32)

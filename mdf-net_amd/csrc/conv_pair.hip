@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "common.h"
+#include "conv_pack.h"
 
 namespace {
 
@@ -400,15 +401,15 @@ __global__ __launch_bounds__(256, MDF_PAIRV_BLOCKS) void conv_pair_valu_kernel(c
 
 }  // namespace
 
-// weights: the packings mdf_conv_pack_weights produces for (Cin_mem 3, Cout 8, 9 taps) and (8, 8, 9 taps); the kernel reads
-// their w-phase segments (behind the plain fragments, as conv_lds.hip's LDS_CASE_RW does)
+// weights: the packings mdf_conv_pack_weights produces for (Cin_mem 3, Cout 8, 9 taps) and (8, 8, 9 taps).  conv_pair_kernel reads
+// their w-phase segments (conv_pack.h: rw_off(), as conv_lds.hip's LDS_CASE_RW does)
 extern "C" int mdf_conv2d_pair_fwd(const float* x, const float* w1pack, const float* alpha1, const float* beta1, const float* w2pack,
                                    const float* alpha2, const float* beta2, float* y, int N, int H, int W, void* stream) {
   MDF_REQUIRE(x && w1pack && alpha1 && beta1 && w2pack && alpha2 && beta2 && y, "null pointer argument");
   MDF_REQUIRE(N > 0 && H > 0 && W > 0, "bad shape");
   MDF_REQUIRE((long long)N * H * W * 8 < (1ll << 31), "output too large for 32-bit offsets");
   {
-    const bool valu = [] { const char* e = getenv("MDF_CONV_PAIR_VALU"); return e ? atoi(e) != 0 : true; }();      // dev A/B and the equality test (read per call)
+    const bool valu = mdf::env_flag("MDF_CONV_PAIR_VALU", true);      // dev A/B and the equality test (read per call)
     if (valu) {
       PairVParams q{};
       q.x = x; q.w1 = w1pack; q.a1 = alpha1; q.b1 = beta1; q.w2 = w2pack; q.a2 = alpha2; q.b2 = beta2; q.y = y;
@@ -428,13 +429,15 @@ extern "C" int mdf_conv2d_pair_fwd(const float* x, const float* w1pack, const fl
   }
   PairParams p{};
   p.x = x; p.a1 = alpha1; p.b1 = beta1; p.a2 = alpha2; p.b2 = beta2; p.y = y;
-  p.w1 = w1pack + 9 * 4 * 16;       // plain fragments of (cin 4, cout 8): 9 taps x 64 lanes x 1
-  p.w2 = w2pack + 9 * 8 * 16;       // (cin 8, cout 8): 9 taps x 64 lanes x 2
+  constexpr mdf::PackLayout L1 = mdf::pack_layout(0, 0, 3, 8, 9), L2 = mdf::pack_layout(0, 0, 8, 8, 9);
+  if (L1.rw == 0 || L2.rw == 0) return mdf::fail(MDF_EUNSUPPORTED, "conv pair: a packed set has no w-phase segment");
+  p.w1 = w1pack + L1.rw_off();      // w-phase fragments of (cin 4, cout 8), behind its plain ones
+  p.w2 = w2pack + L2.rw_off();      // w-phase fragments of (cin 8, cout 8)
   p.N = N; p.H = H; p.W = W;
   p.strips = (W + kOW - 1) / kOW;
   // many short blocks: two are resident per CU (512 in all), so with ~1000 long ones the last few ran alone for a third of the
   // kernel's time (1040 blocks = 2.03 rounds); a segment costs 2 extra intermediate rows and a prologue, so not too many either
-  static const long long target = [] { const char* e = getenv("MDF_PAIR_BLOCKS"); return (e && atoll(e) > 0) ? atoll(e) : 2048ll; }();   // dev A/B (sweep at cfg2: 1024 265 us, 2048 252, 4096 265, 8192 286)
+  static const long long target = mdf::env_pos("MDF_PAIR_BLOCKS", 2048);   // dev A/B (sweep at cfg2: 1024 265 us, 2048 252, 4096 265, 8192 286)
   long long segs = target / ((long long)N * p.strips);
   if (segs > H / 16) segs = H / 16;
   if (segs < 1) segs = 1;

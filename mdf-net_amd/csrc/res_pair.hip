@@ -11,6 +11,7 @@
 // result is BIT-IDENTICAL to them (tests/test_conv2d_gpu.py).
 #include <cstdlib>
 #include "common.h"
+#include "conv_pack.h"
 
 namespace {
 
@@ -225,7 +226,7 @@ extern "C" int mdf_refine_head_fwd(const float* depth, const float* lo, const fl
 }
 
 // weights: the packings mdf_conv_pack_weights produces for (Cin_mem 8, Cout 8, 9 taps); the kernel reads their w-phase segments
-// (behind the plain fragments, as conv_lds.hip's LDS_CASE_RW and conv_pair.hip do)
+// (conv_pack.h: rw_off(), as conv_lds.hip's LDS_CASE_RW and conv_pair.hip do)
 extern "C" int mdf_conv2d_res_pair_fwd(const float* x, const float* wa_pack, const float* wb_pack, float scale, float* y, int N, int H,
                                        int W, void* stream) {
   MDF_REQUIRE(x && wa_pack && wb_pack && y, "null pointer argument");
@@ -234,12 +235,14 @@ extern "C" int mdf_conv2d_res_pair_fwd(const float* x, const float* wa_pack, con
   MDF_REQUIRE((long long)N * H * W * 8 < (1ll << 31), "map too large for 32-bit offsets");
   ResPairParams p{};
   p.x = x; p.y = y; p.scale = scale;
-  p.wa = wa_pack + 9 * 8 * 16;       // behind the plain fragments of (cin 8, cout 8): 9 taps x 64 lanes x 2
-  p.wb = wb_pack + 9 * 8 * 16;
+  constexpr mdf::PackLayout L = mdf::pack_layout(0, 0, 8, 8, 9);
+  if (L.rw == 0) return mdf::fail(MDF_EUNSUPPORTED, "res pair: the packed set has no w-phase segment");
+  p.wa = wa_pack + L.rw_off();       // w-phase fragments of (cin 8, cout 8), behind its plain ones
+  p.wb = wb_pack + L.rw_off();
   p.N = N; p.H = H; p.W = W;
   p.strips = (W + kOW - 1) / kOW;
   // enough blocks to fill the chip a few times over (two are resident per CU: 68 KB of LDS); a segment costs 2 extra intermediate rows
-  static const long long target = [] { const char* e = getenv("MDF_RES_PAIR_BLOCKS"); return (e && atoll(e) > 0) ? atoll(e) : 1024ll; }();   // dev A/B
+  static const long long target = mdf::env_pos("MDF_RES_PAIR_BLOCKS", 1024);   // dev A/B
   long long segs = target / ((long long)N * p.strips);
   if (segs > H / 16) segs = H / 16;
   if (segs < 1) segs = 1;

@@ -533,12 +533,12 @@ int launch_win(Params& p, hipStream_t st) {
   const int hw = p.g.h * p.g.w;
   p.nblk_x = (hw + ppb - 1) / ppb;
   int dch = 512 / (p.n_src * ppb);
-  if (const char* e = getenv("MDF_WARP_DCHUNK")) { if (atoi(e) > 0) dch = atoi(e); }   // dev A/B
+  dch = mdf::env_pos("MDF_WARP_DCHUNK", dch);   // dev A/B
   if (dch < 1) dch = 1;
   if (dch > p.D) dch = p.D;
   p.dchunk = dch;
   int pool_kb = 64;
-  if (const char* e = getenv("MDF_WARP_POOL_KB")) { if (atoi(e) > 0) pool_kb = atoi(e); }   // dev A/B
+  pool_kb = mdf::env_pos("MDF_WARP_POOL_KB", pool_kb);   // dev A/B
   const size_t tab_bytes = (size_t)dch * p.n_src * ppb * sizeof(TapXY);
   const size_t lds = tab_bytes + (size_t)pool_kb * 1024;
   if (lds > 150 * 1024) return MDF_EUNSUPPORTED;
@@ -654,8 +654,7 @@ extern "C" int mdf_warp_aggregate_vec_fwd(const float* ref_fea, const float* con
   p.B = B; p.D = D; p.n_src = n_src; p.hypos_per_pixel = hypos_per_pixel; p.out_ndhwc = (cost_layout == MDF_VOL_NDHWC);
   // LDS-staged source windows: bit-identical, but measured SLOWER than the L1 gather on MI355X (r02: 1.37 ms vs 0.80 ms per
   // cfg2 view at a 32-KiB pool, 3.0 ms at 64 KiB -- the kernel lives on occupancy), so it is opt-in
-  const char* we = getenv("MDF_WARP_WINDOW");
-  if (we && atoi(we) != 0) {
+  if (mdf::env_flag("MDF_WARP_WINDOW", false)) {
     int rc = MDF_EUNSUPPORTED;
     if (C == 64) rc = launch_win<64>(p, (hipStream_t)stream);
     else if (C == 32) rc = launch_win<32>(p, (hipStream_t)stream);
@@ -663,13 +662,13 @@ extern "C" int mdf_warp_aggregate_vec_fwd(const float* ref_fea, const float* con
     if (rc != MDF_EUNSUPPORTED) return rc;
   }
   {
-    const char* e8 = getenv("MDF_WARP_VEC8");      // dev A/B (read per call): 8 channels per lane
-    if (!e8 || atoi(e8) != 0) {
+    const int v8 = mdf::env_int("MDF_WARP_VEC8", 1);      // dev A/B (read per call): 8 channels per lane
+    if (v8 != 0) {
       int rc = MDF_EUNSUPPORTED;
       // (in a cfg2 forward: C 64 243 -> 233 us, C 32 254 -> 250 us; C 16 -- two lanes per pixel, a 128-pixel tile -- 204 -> 221 us: not used)
       if (C == 64) rc = launch_vec8<64>(p, (hipStream_t)stream);
       else if (C == 32) rc = launch_vec8<32>(p, (hipStream_t)stream);
-      else if (C == 16 && e8 && atoi(e8) == 2) rc = launch_vec8<16>(p, (hipStream_t)stream);
+      else if (C == 16 && v8 == 2) rc = launch_vec8<16>(p, (hipStream_t)stream);
       if (rc != MDF_EUNSUPPORTED) return rc;
     }
   }
@@ -697,8 +696,7 @@ extern "C" int mdf_warp_aggregate_pairdiff_fwd(const float* ref_diff, const floa
   // lane: G 32 174 | 186 us, G 16 181 | 183 us, G 8 136 | 167 us (full features: 247, 274, 176 us).  With 8 the kernel needs 126
   // registers (4 waves per SIMD, as the full-feature kernels) against 85 (5 waves), and at G = 8 a pixel is one lane with a 256-pixel
   // tile: four (pixel, view) pairs per thread in phase A, one plane per table chunk.
-  int gpl = 4;
-  if (const char* e = getenv("MDF_PAIRDIFF_GPL")) { if (atoi(e) == 4 || atoi(e) == 8) gpl = atoi(e); }   // dev A/B (read per call)
+  const int gpl = mdf::env_int("MDF_PAIRDIFF_GPL", 4) == 8 ? 8 : 4;   // dev A/B (read per call)
   if (gpl == 8) {
     int rc = MDF_EUNSUPPORTED;
     if (G == 32) rc = launch_pairdiff<32, 8>(p, st);

@@ -381,18 +381,17 @@ int launch_bwd(TrainParams& p, int C, hipStream_t st) {
   p.nblk_x = bwd_tile_blocks(C, p.g.w, p.g.h);
   // tap-table entries per block: uniform hypotheses (stage 0) sweep an epipolar segment and amortise a view's window over more
   // planes; per-pixel hypotheses take a whole view's planes anyway
-  static const int tab_env = [] { const char* e = getenv("MDF_WARP_BWD_TAB"); return (e && atoi(e) > 0) ? atoi(e) : 0; }();   // dev A/B
+  static const int tab_env = mdf::env_pos("MDF_WARP_BWD_TAB", 0);   // dev A/B
   const int tab_entries = tab_env ? tab_env : (p.hypos_per_pixel ? 512 : 1024);
   int dch = tab_entries / (p.n_src * ppb);
   if (dch < 1) dch = 1;
   // depth slices of the scatter: with per-pixel hypotheses a pixel's planes hit the same few texels, and their tap sums stay in
   // registers across ALL the planes a block walks -- slicing the depth range costs more than the extra blocks bring (cfg3 stage 2:
   // 178 us unsliced, 284 in two slices); uniform hypotheses (stage 0, 432 blocks at cfg3) take three slices (162 us; 192 in two)
-  static const int target_env = [] { const char* e = getenv("MDF_WARP_BWD_BLOCKS"); return (e && atoi(e) > 0) ? atoi(e) : 0; }();   // dev A/B
+  static const int target_env = mdf::env_pos("MDF_WARP_BWD_BLOCKS", 0);   // dev A/B
   const int nz = depth_slices(p, dch, target_env ? target_env : (p.hypos_per_pixel ? 768 : 1024));
   p.dchunk = equal_chunks(p.dslice, dch);
-  const char* dbg = getenv("MDF_WARP_BWD_ATOMIC");      // read per call: tests flip it inside one process
-  p.all_atomic = (dbg && atoi(dbg) > 0) ? atoi(dbg) : 0;     // bit 0: all-atomic window updates; bit 1: timing experiment without the flush
+  p.all_atomic = mdf::env_pos("MDF_WARP_BWD_ATOMIC", 0);     // read per call: tests flip it inside one process.  bit 0: all-atomic window updates; bit 1: timing experiment without the flush
   const size_t lds = (size_t)p.dchunk * p.n_src * ppb * sizeof(TapXY) + (size_t)kWinFloats * sizeof(float);
   dim3 grid(p.nblk_x, p.B, nz), block(kThreads);
   switch (C) {
@@ -409,10 +408,10 @@ int launch_train(TrainParams& p, int C, hipStream_t st) {
   const int lpp = C / 4, ppb = kThreads / lpp;
   const int hw = p.g.h * p.g.w;
   p.nblk_x = (hw + ppb - 1) / ppb;
-  static const int tab_env = [] { const char* e = getenv("MDF_WARP_TRAIN_TAB"); return (e && atoi(e) > 0) ? atoi(e) : 512; }();   // dev A/B
+  static const int tab_env = mdf::env_pos("MDF_WARP_TRAIN_TAB", 512);   // dev A/B
   int dch = tab_env / (p.n_src * ppb);
   if (dch < 1) dch = 1;
-  static const int target_env = [] { const char* e = getenv("MDF_WARP_TRAIN_BLOCKS"); return (e && atoi(e) > 0) ? atoi(e) : 0; }();   // dev A/B
+  static const int target_env = mdf::env_pos("MDF_WARP_TRAIN_BLOCKS", 0);   // dev A/B
   const int nz = depth_slices(p, dch, target_env ? target_env : (p.hypos_per_pixel ? 1024 : 2048));
   p.dchunk = equal_chunks(p.dslice, dch);
   const size_t lds = (size_t)p.dchunk * p.n_src * ppb * sizeof(TapEntry);

@@ -200,13 +200,13 @@ template <bool VAR>
 int launch_var_bwd(VarBwdParams& p, int C, hipStream_t st) {
   const int lpp = C / 4, ppb = kThreads / lpp;
   p.nblk_x = bwd_tile_blocks(C, p.g.w, p.g.h);
-  static const int tab_env = [] { const char* e = getenv("MDF_VAR_BWD_TAB"); return (e && atoi(e) > 0) ? atoi(e) : 1024; }();   // dev A/B
+  static const int tab_env = mdf::env_pos("MDF_VAR_BWD_TAB", 1024);   // dev A/B
   int dch = tab_env / (p.n_src * ppb);        // tap-table entries (32 B each) per block
   if (dch > kPlanes) dch = kPlanes;
   if (dch < 1) dch = 1;
   // depth slices (gridDim.z): the small maps of the first stage give a few hundred blocks only.  The chunks of a slice are not
   // equalised here (equal_chunks): they are at most kPlanes planes anyway
-  static const int target_env = [] { const char* e = getenv("MDF_VAR_BWD_BLOCKS"); return (e && atoi(e) > 0) ? atoi(e) : 1024; }();   // dev A/B
+  static const int target_env = mdf::env_pos("MDF_VAR_BWD_BLOCKS", 1024);   // dev A/B
   const int nz = depth_slices(p, dch, target_env);
   p.dchunk = dch;
   const size_t lds = (size_t)dch * p.n_src * ppb * sizeof(TapXY) + (size_t)kWinFloats * sizeof(float);

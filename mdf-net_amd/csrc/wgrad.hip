@@ -536,18 +536,10 @@ int mdf_wgrad_lds_dispatch(const float* small_, const float* big, float* workspa
                            int stride, int ksize, int is3d, float* zero_out, int zero_n, void* stream);
 // blocks per launch: every block writes one partial tile set to the slab (PMC: 2 GB written + 2 GB re-read per cfg3 step at
 // 2048 blocks), so no more blocks than it takes to fill the chip a few times over
-static int wgrad_target_blocks() {
-  static const int n = [] { const char* e = getenv("MDF_WGRAD_BLOCKS"); return (e && atoi(e) > 0) ? atoi(e) : 1024; }();
-  return n;
-}
-static long long wgrad_slab_cap_bytes() {     // partial-tile bytes per launch (written by the blocks, read again by the sum)
-  static const long long n = [] { const char* e = getenv("MDF_WGRAD_SLAB_MIB"); return (long long)((e && atoi(e) > 0) ? atoi(e) : 16) << 20; }();   // dev A/B
-  return n;
-}
-static bool wgrad_use_lds() {
-  static const bool on = [] { const char* e = getenv("MDF_WGRAD_LDS"); return e ? atoi(e) != 0 : true; }();   // dev A/B
-  return on;
-}
+static int wgrad_target_blocks() { static const int n = mdf::env_pos("MDF_WGRAD_BLOCKS", 1024); return n; }
+// partial-tile bytes per launch (written by the blocks, read again by the sum)
+static long long wgrad_slab_cap_bytes() { static const long long n = mdf::env_pos("MDF_WGRAD_SLAB_MIB", 16) << 20; return n; }   // dev A/B
+static bool wgrad_use_lds() { static const bool on = mdf::env_flag("MDF_WGRAD_LDS", true); return on; }   // dev A/B
 
 extern "C" int64_t mdf_conv3d_wgrad_workspace(int B, int Ds, int Hs, int Ws, int A, int Bc) {
   if (B < 1 || Ds < 1 || Hs < 1 || Ws < 1 || A < 1 || Bc < 1) return 0;
@@ -597,7 +589,7 @@ static int conv3d_wgrad_impl(const float* small_, const float* big, float* dw, f
   p.zero_n = n;
   int gx_used = gx;
   int rc_lds = MDF_EUNSUPPORTED;
-  static const bool a1_valu = [] { const char* e = getenv("MDF_WGRAD_A1_VALU"); return e ? atoi(e) != 0 : true; }();   // dev A/B
+  static const bool a1_valu = mdf::env_flag("MDF_WGRAD_A1_VALU", true);   // dev A/B
   if (A == 1 && (Bc == 8 || Bc == 16) && stride == 1 && a1_valu) {
     const long long vpb = 256 / (Bc / 4);
     long long g = ((long long)B * Ds * Hs * Ws + vpb - 1) / vpb;     // at most one voxel group per block and iteration ...

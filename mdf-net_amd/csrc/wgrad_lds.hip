@@ -368,7 +368,7 @@ extern "C" int mdf_wgrad_batch_flush(void* stream) {
   for (size_t i = 0; i < jobs.size(); ++i) {
     if (done[i]) continue;
     WgradBatch tb{};
-    tb.zfast = [] { const char* e = getenv("MDF_WGRAD_ZFAST"); return e ? atoi(e) : 1; }();   // dev A/B (read per flush)
+    tb.zfast = mdf::env_int("MDF_WGRAD_ZFAST", 1);   // dev A/B (read per flush)
     int blocks = 0;
     size_t lds = 0;
     for (size_t k = i; k < jobs.size() && tb.njobs < kWgradBatchMax; ++k) {
@@ -407,7 +407,7 @@ int mdf_wgrad_lds_dispatch(const float* small_, const float* big, float* workspa
   const int KH = is3d ? 3 : 1, KW = ksize;
   p.ntaps_total = is3d ? 27 : ksize * ksize;
   // tap packing for the few-channel layers (see the kernel): shifts of `small` in the rows, of `big` in the columns
-  static const bool pack_on = [] { const char* e = getenv("MDF_WGRAD_PACK"); return e ? atoi(e) != 0 : true; }();   // dev A/B
+  static const bool pack_on = mdf::env_flag("MDF_WGRAD_PACK", true);   // dev A/B
   p.pa = p.pb = 1;
   if (pack_on && stride == 1 && ksize == 3) {
     if (A <= 8) p.pa = 2;
@@ -417,7 +417,7 @@ int mdf_wgrad_lds_dispatch(const float* small_, const float* big, float* workspa
   // tile = TH rows x tv voxels.  tv: a multiple of 16 voxels, as wide as the register staging and ~72 KiB of LDS allow (more MFMAs
   // per barrier pair), chosen to waste the fewest voxels of the row's last tile; TH in {1, 2, 4} rows where rows are short
   // (3-D with TH > 1: stride 1 only -- the staged `big` rows of neighbouring output rows must be neighbours).
-  static const int th_max = [] { const char* e = getenv("MDF_WGRAD_TH"); return (e && atoi(e) > 0) ? atoi(e) : 2; }();   // dev A/B (4 rows measured slower than 2 on every cfg3 shape: fewer, fatter tiles starve the chip)
+  static const int th_max = mdf::env_pos("MDF_WGRAD_TH", 2);   // dev A/B (4 rows measured slower than 2 on every cfg3 shape: fewer, fatter tiles starve the chip)
   int best_tv = 0, best_th = 1;
   long long best_cost = 0;
   size_t best_lds = 0;
@@ -433,7 +433,7 @@ int mdf_wgrad_lds_dispatch(const float* small_, const float* big, float* workspa
       const int WB = tv * stride + KW - 1;
       if ((tv + hal) * (A / 4) > ns * 256 || WB * (Bc / 4) > npr * 256) break;    // register staging capacity
       const size_t lds = (size_t)(th * (tv + hal) * p.AS + (nbr * WB + 1) * p.BS) * sizeof(float);
-      static const int lds_kb = [] { const char* e = getenv("MDF_WGRAD_LDS_KB"); return (e && atoi(e) > 0) ? atoi(e) : 0; }();   // dev A/B
+      static const int lds_kb = mdf::env_pos("MDF_WGRAD_LDS_KB", 0);   // dev A/B
       if (lds > (size_t)(lds_kb ? lds_kb : (th == 1 ? 72 : 80)) * 1024) break;   // two blocks per CU
       const int rounds = (th * (tv / 16) + p.split - 1) / p.split;                 // chunks of the busiest wave
       const long long tiles = (long long)((Hs + th - 1) / th) * ((Ws + hal + tv - 1) / tv);

@@ -497,7 +497,7 @@ int launch_wino2d(Wino2dParams& p, hipStream_t st) {
     attr_done = true;
   }
   long long grid = 256;      // one block per CU
-  if (const char* g = getenv("MDF_WINO2D_GRID")) { if (atoi(g) > 0) grid = atoi(g); }   // dev
+  grid = mdf::env_pos("MDF_WINO2D_GRID", grid);   // dev
   if (grid > tiles / 2) grid = tiles / 2;
   if (grid < 1) grid = 1;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), C::LDS_BYTES, st, p);
@@ -523,14 +523,14 @@ int mdf_wino2d_dispatch(const float* x, const float* wpack_wino, const float* al
 }
 
 // The 5x5 stride-2 layers over the parity images of their input: x [B,2*Ho,2*Wo,Cin_mem], y [B,Ho,Wo,Cout]; wpack_k5w = the layer's
-// transform-domain fragments over 4*Cin_mem logical input channels (conv3d.hip: k5w_built).
+// transform-domain fragments over 4*Cin_mem logical input channels (conv_pack.h: k5w_built).
 int mdf_wino2d_s2d_dispatch(const float* x, const float* wpack_k5w, const float* alpha, const float* beta, float* y, int B, int Ho, int Wo,
                             int Cin_mem, int Cout, int relu, void* stream) {
   Wino2dParams p{};
   p.x = x; p.wpack = wpack_k5w; p.alpha = alpha; p.beta = beta; p.res = nullptr; p.res_scale = 0.f; p.y = y;
   p.B = B; p.H = Ho; p.W = Wo; p.relu = relu;
   if ((long long)B * Ho * Wo * 4 * Cin_mem * 4 >= (1ll << 31)) return MDF_EUNSUPPORTED;     // byte offsets inside a patch are 31-bit
-  const bool skip = [] { const char* e = getenv("MDF_WINO2D_SKIP"); return e ? atoi(e) != 0 : true; }();   // 0: every step, the zero ones too (the bit-identity checker; read per call)
+  const bool skip = mdf::env_flag("MDF_WINO2D_SKIP", true);   // 0: every step, the zero ones too (the bit-identity checker; read per call)
   hipStream_t st = (hipStream_t)stream;
   // 32 -> 64: 98 live steps + 2 kept zero steps = 4 buffers x 25 (two cout tiles per wave: a ring of 7 buffers, 56 registers, spills)
   if (Cin_mem == 32 && Cout == 64) return skip ? launch_wino2d<128, 64, true, true, 4, 2>(p, st) : launch_wino2d<128, 64, true, false>(p, st);

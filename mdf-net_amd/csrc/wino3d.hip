@@ -424,7 +424,7 @@ int launch_wino3d(Wino3dParams& p, hipStream_t st) {
   }
   // one block per CU (192 accumulator registers per lane); every block at least ~4 planes so that a segment's two halo planes stay a fraction
   long long grid = 256;
-  if (const char* g = getenv("MDF_WINO3D_GRID")) { if (atoi(g) > 0) grid = atoi(g); }   // dev
+  grid = mdf::env_pos("MDF_WINO3D_GRID", grid);   // dev
   if (grid > p.total / 4) grid = p.total / 4;
   if (grid < 1) grid = 1;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), C::LDS_BYTES, st, p);

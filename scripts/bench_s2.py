@@ -1,4 +1,4 @@
-"""The stride-2 3-D layers of cfg2's regularisers: us per launch (MDF_CONV_LDS_S2_MIN_VOXELS=-1: conv3d.hip's kernel).  dev tool"""
+"""The stride-2 3-D layers of cfg2's regularisers: us per launch (MDF_CONV3D_WLDS=0 MDF_CONV3D_WLDS8=0: conv3d_kernel instead of the weights-in-LDS form).  dev tool"""
 import os, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [R + '/mdf-net_amd']

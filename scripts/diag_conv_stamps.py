@@ -41,7 +41,7 @@ for name, ci, co, k, st, b, h, w in [("refine 8->8", 8, 8, 3, 1, 1, 592, 800), (
     x = torch.randn(b, h, w, ci, device=dev)
     wp = ops.pack_conv2d_weight(torch.randn(co, ci, k, k, device=dev) * 0.1)
     for ev in ("0",):
-        os.environ["MDF_CONV2D_PREFETCH_EARLY"] = ev
+        os.environ["MDF_CONV_PREFETCH_EARLY"] = ev
         for _ in range(2): ops.conv2d_nhwc(x, wp, ci, co, k, st)
         torch.cuda.synchronize()
         buf = (ctypes.c_ulonglong * 8)()
