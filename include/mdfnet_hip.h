@@ -369,6 +369,32 @@ long long mdf_pts_icp_workspace(void);
 int mdf_pts_icp_sums(const double* src, long long n, const double* tgt, long long nt, const int* nearest, const double* dist2,
                      double threshold, void* workspace, long long ws_bytes, double* out, void* stream);
 
+/* ---- Point-cloud post-processing (k nearest neighbours, normal estimation), fp64 throughout ------------------------------------
+ * The counterparts of the Open3D calls of the reference's tools/pcd/fusion.py (estimate_normals with its default 30-neighbour search,
+ * compute_nearest_neighbor_distance), stated here and not measured against an Open3D build.  The spatial index, the distance
+ * formula and the rounding rules are those of the DTU section above.
+ *   mdf_pts_knn        the k nearest index points of every query, 1 <= k <= MDF_PTS_KNN_MAX.  Row i of nbr [m][k] int32 holds the
+ *                      INPUT indices of query i's min(k, n) nearest points in ascending (d^2, input index) order, a total order:
+ *                      ties on d^2 go to the lowest input index, as in mdf_pts_nn.  A point identical to the query is a neighbour
+ *                      like any other, so a self-query has the point itself (or a lower-indexed duplicate) in slot 0.  Slots past
+ *                      min(k, n) hold -1 and +inf.  dist2 [m][k] (or NULL): the d^2 of each slot; visits [m] (or NULL): leaves
+ *                      visited.  Queries as an array or as an index, as for mdf_pts_nn.  A subtree is walked while its box
+ *                      distance^2 is <= the k-th best so far (an equal distance may win on the index), so a cloud made of many
+ *                      identical points degrades to a linear walk.
+ *   mdf_pts_normals    a self-query over the index's own points that keeps no neighbour list in memory.  With N the
+ *                      k_eff = min(k, n) neighbours of point i in the order above: nine sums over N in that order, each from 0 and
+ *                      every product rounded once (x, y, z, xx, xy, xz, yy, yz, zz), each divided by k_eff, then
+ *                      C_ab = E[ab] - E[a] * E[b], written to cov [n][6] (xx, xy, xz, yy, yz, zz; or NULL).  normals [n][3]: the
+ *                      unit eigenvector of C for its smallest eigenvalue (cyclic Jacobi, a fixed number of sweeps), or (0, 0, 1)
+ *                      when k_eff < 3.  dirs [n][3] fp32 (or NULL) orients it: s = ((nx*dx) + ny*dy) + nz*dz with dirs widened to
+ *                      double; the normal is kept when s > 0 and negated otherwise (an exact 0 negates).  normals, cov and dirs
+ *                      are in input order.                                                                                    */
+#define MDF_PTS_KNN_MAX 32
+int mdf_pts_knn(const void* index, long long n, long long index_bytes, const void* qindex, const double* queries, long long m,
+                long long qindex_bytes, int k, int* nbr, double* dist2, int* visits, void* stream);
+int mdf_pts_normals(const void* index, long long n, long long index_bytes, int k, const float* dirs, double* normals, double* cov,
+                    void* stream);
+
 /* =====================================================================================================
  * Training path (BASELINE config 3; train.py:36-45 -> loss.backward()).  The reference has no explicit backward:
  * autograd differentiates the op chains cited above.  Each entry below is the hand-written forward-in-train-mode or

@@ -82,6 +82,8 @@ SIGNATURES = {
     "mdf_pts_voxel_downsample": (c_int, [c_fp, c_fp, c_int, c_i64, ctypes.c_double, c_fp, c_i64, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "mdf_pts_icp_workspace": (c_i64, []),
     "mdf_pts_icp_sums": (c_int, [c_fp, c_i64, c_fp, c_i64, c_fp, c_fp, ctypes.c_double, c_fp, c_i64, c_fp, c_fp]),
+    "mdf_pts_knn": (c_int, [c_fp, c_i64, c_i64, c_fp, c_fp, c_i64, c_i64, c_int, c_fp, c_fp, c_fp, c_fp]),
+    "mdf_pts_normals": (c_int, [c_fp, c_i64, c_i64, c_int, c_fp, c_fp, c_fp, c_fp]),
     "mdf_bn_stats_fwd": (c_int, [c_fp, c_i64, c_int, c_int, c_fp, c_fp]),
     "mdf_bn_finalize_fwd": (c_int, [c_fp, c_fp, c_fp, ctypes.c_float, ctypes.c_float, c_i64, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_fp]),
     "mdf_bn_relu_apply_fwd": (c_int, [c_fp, c_fp, c_fp, c_fp, c_i64, c_int, c_int, c_fp]),
@@ -166,6 +168,12 @@ def pcd_fuse(*args, **kwargs):
     """Point-cloud fusion of one scan (ops.pcd_fuse; the reference's tools/pcd/fusion.py:get_cloud)."""
     from .ops import pcd_fuse as _pcd_fuse
     return _pcd_fuse(*args, **kwargs)
+
+
+def estimate_normals(*args, **kwargs):
+    """Normals of a point cloud from its k nearest neighbours (ops.estimate_normals; Open3D's estimate_normals in the reference)."""
+    from .ops import estimate_normals as _estimate_normals
+    return _estimate_normals(*args, **kwargs)
 
 
 def dtu_eval_scan(*args, **kwargs):

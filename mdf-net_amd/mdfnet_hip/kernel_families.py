@@ -63,6 +63,8 @@ KERNEL_FAMILY = {
     "pts_nn_idx_kernel": POINT_EVAL, "pts_transform_kernel": POINT_EVAL, "pts_crop_kernel": POINT_EVAL, "pts_vox_key_kernel": POINT_EVAL,
     "pts_vox_chunk_sum_kernel": POINT_EVAL, "pts_vox_offsets_kernel": POINT_EVAL, "pts_vox_mean_kernel": POINT_EVAL,
     "pts_icp_moment_kernel": POINT_EVAL, "pts_icp_final_kernel": POINT_EVAL,
+    # point_eval.hip (point-cloud post-processing: k nearest neighbours, normal estimation)
+    "pts_knn_kernel": POINT_EVAL, "pts_normals_kernel": POINT_EVAL,
     # loss.hip
     "masked_smooth_l1_reduce_kernel": CONTROL, "masked_smooth_l1_finalize_kernel": CONTROL, "masked_smooth_l1_bwd_kernel": CONTROL,
     "masked_smooth_l1_reduce_multi_kernel": CONTROL, "masked_smooth_l1_bwd_multi_kernel": CONTROL, "adam_step_kernel": CONTROL,

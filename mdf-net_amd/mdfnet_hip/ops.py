@@ -770,6 +770,7 @@ PCD_CAM_STRIDE = 64
 PCD_STEPS = ("prob", "vis1", "vis_fusion", "vis2", "ave", "vis3", "seg")   # index k of a step == its MDF_PCD_STEP_* (prob: 0)
 PCD_MAX_SOURCES = 64
 PCD_PROB_THRESHOLD = 0.8
+PCD_NORMAL_KNN = 30            # Open3D's estimate_normals() default: KDTreeSearchParamKNN(knn=30)
 
 
 def pcd_cameras(K, E):
@@ -820,19 +821,34 @@ def pcd_steps(depths, masks, cams, srcs, need, first, last):
 
 
 def pcd_fuse(depths, probs, images, K, E, src_table, view=10, vthresh=4, normals=False, downsample=None, stages=None):
-    """Fuse one scan's depth maps into a point cloud (the reference's tools/pcd/fusion.py:get_cloud, stages 1-6).
+    """Fuse one scan's depth maps into a point cloud (the reference's tools/pcd/fusion.py:get_cloud, stages 1-8).
     depths, probs: GPU fp32 [N,H,W]; images: GPU uint8 [N,H,W,3] RGB; K [N,3,3], E [N,4,4]: host arrays; src_table: per view
     the list of its source view indices (pair.txt order, already restricted to views of the scan), of which the first `view`
     are used.  stages: None runs the whole pipeline; k in 1..7 stops after step PCD_STEPS[k-1] and returns that state only.
     -> dict(depths [N,H,W] fp32, masks [N,H,W] bool, counts [N] int32, and with the whole pipeline xyz [M,3] fp32,
     rgb [M,3] uint8, dirs [M,3] fp32 (camera centre - point)), all on the GPU, points in view then row-major pixel order.
+    normals=True (stage 7) adds normals [M,3] fp64: estimate_normals over the points with k = PCD_NORMAL_KNN neighbours, oriented
+    towards the camera by dirs.  downsample=d (stage 8) replaces the points by the means of a voxel grid of side d (d = -1: the
+    90th percentile of nn_spacing, numpy's linear rule; needs M >= 2 and a positive result): xyz is the cell means rounded to
+    fp32, rgb = uint8(round_half_away(clamp(mean of fp32(u8) / fp32(255), 0, 1) * 255)), normals the cell means (not
+    renormalised), cells in ascending (x, y, z) cell order; `voxel` = the side used is added and dirs is dropped.
+    Without either the result is what stages 1-6 give.  Neither Open3D call has been compared with an Open3D build.
     Device memory beyond the inputs: mdf_pcd_fuse_workspace (13 B per view-pixel + 8 (view + 3) B per pixel of one view)
-    plus 27 B per point.  Normal estimation and voxel downsampling are not available yet: normals=True or a downsample
-    raises."""
+    plus 27 B per point; stage 7 adds the fp64 points, the index (point_index: 52 B a point + 96 B a leaf slot) and the
+    normals, 100 B a point in all, and no neighbour list; stage 8 adds 8 B a point for the spacing and its sorted copy, the
+    attribute columns (24 or 48 B a point), mdf_pts_voxel_workspace (32 B a point + the sort tables) and the worst-case outputs
+    (28 B + 8 B per attribute column a point)."""
+    import math
     import numpy as np
-    if normals or downsample is not None:
-        raise NotImplementedError("pcd_fuse: normal estimation and voxel downsampling are not implemented; "
-                                  "call with normals=False, downsample=None")
+    if downsample is not None:
+        downsample = float(downsample)
+        if downsample != -1.0 and not (math.isfinite(downsample) and downsample > 0):
+            raise ValueError(f"pcd_fuse: downsample={downsample} must be finite and > 0, or -1 for the 90th percentile of the "
+                             "nearest-neighbour spacing")
+        if stages is not None:
+            raise ValueError("pcd_fuse: downsample needs the whole pipeline (stages=None)")
+    if normals and stages is not None:
+        raise ValueError("pcd_fuse: normals need the whole pipeline (stages=None)")
     _need_gpu(depths, probs, images)
     if depths.dim() != 3 or tuple(probs.shape) != tuple(depths.shape) or tuple(images.shape) != (*depths.shape, 3) \
             or images.dtype != torch.uint8:
@@ -865,7 +881,44 @@ def pcd_fuse(depths, probs, images, K, E, src_table, view=10, vthresh=4, normals
                                  view, ws.data_ptr(), xyz.data_ptr(), rgb.data_ptr(), dirs.data_ptr(), m, _stream(depths)),
              tag=f"{w}x{h} n{n}", work={"bytes": 5.0 * n * h * w + 27.0 * m, "bound": "hbm"})
     out.update(xyz=xyz, rgb=rgb, dirs=dirs)
+    if not normals and downsample is None:
+        return out
+    xyz64 = xyz.double()
+    index = point_index(xyz64)
+    if normals:
+        out["normals"] = estimate_normals(index, dirs=dirs, k=PCD_NORMAL_KNN)
+    if downsample is not None:
+        voxel = pcd_voxel_size(index) if downsample == -1.0 else downsample
+        attrs = (rgb.float() / 255.0).double()               # fp32(u8) / fp32(255), widened
+        if normals:
+            attrs = torch.cat([attrs, out["normals"]], 1)
+        vxyz, vattrs = voxel_downsample(xyz64, voxel, attrs=attrs)
+        c = vattrs[:, :3].clamp(0.0, 1.0) * 255.0
+        r = torch.floor(c)
+        out.update(xyz=vxyz.float(), rgb=(r + ((c - r) >= 0.5).double()).to(torch.uint8), voxel=voxel)
+        if normals:
+            out["normals"] = vattrs[:, 3:6].contiguous()
+        del out["dirs"]
     return out
+
+
+def pcd_voxel_size(index):
+    """The voxel side of pcd_fuse(downsample=-1): numpy.percentile(nn_spacing(index), 90) with its linear interpolation at
+    position 0.9 (M - 1), from one torch.sort on the GPU and the two values around that position."""
+    m = index.n
+    if m < 2:
+        raise ValueError(f"pcd_fuse: downsample=-1 needs at least 2 points, got {m}")
+    s, _ = torch.sort(nn_spacing(index))
+    pos = (m - 1) * (90 / 100)                                 # numpy's virtual index of the linear method
+    lo = int(pos // 1)
+    t = pos - lo
+    lo, hi = min(max(lo, 0), m - 1), min(max(lo + 1, 0), m - 1)
+    a, b = (float(v) for v in s[[lo, hi]].tolist())
+    d = b - a
+    voxel = b - d * (1 - t) if t >= 0.5 else a + d * t       # numpy's two-sided lerp
+    if not (voxel > 0 and voxel < float("inf")):
+        raise ValueError(f"pcd_fuse: the 90th percentile of the nearest-neighbour spacing is {voxel}; a positive voxel size is needed")
+    return voxel
 
 
 # --------------------------------------------------------------------------- DTU point-cloud evaluation (the MATLAB scorer)
@@ -1119,6 +1172,68 @@ def nn_search(index, queries, cap, return_d2=False, return_visits=False):
                             visits.data_ptr() if return_visits else None, _stream(dist)),
              tag=f"n{index.n} m{m}", work={"queries": float(m), "bound": "valu"})
     return (dist, nearest) + ((d2,) if return_d2 else ()) + ((visits,) if return_visits else ())
+
+
+KNN_MAX = 32                   # MDF_PTS_KNN_MAX
+
+
+def _queries_arg(queries):
+    if isinstance(queries, PointIndex):
+        return queries.n, queries.buf.data_ptr(), None, queries.nbytes
+    _need_gpu(queries)
+    q = _pts64(queries)
+    return q.shape[0], None, q, 0
+
+
+def knn_search(index, queries, k, return_d2=False, return_visits=False):
+    """Exact k nearest neighbours of every query among the index's points (mdf_pts_knn), 1 <= k <= 32: -> nbr [m,k] int32 on the
+    GPU, row i = the positions (in the array the index was built from) of query i's min(k, n) nearest points in ascending
+    (d^2, position) order, so ties on d^2 go to the lowest position and a point identical to the query counts like any other;
+    slots past min(k, n) hold -1.  queries: GPU [m,3] or a PointIndex (walked in Morton order, results at the input positions).
+    return_d2 appends d^2 [m,k] (+inf in the empty slots), return_visits the leaves visited per query."""
+    if not isinstance(index, PointIndex):
+        raise TypeError("knn_search: index must come from point_index()")
+    m, qidx, q, qbytes = _queries_arg(queries)
+    k = int(k)
+    dev = index.device
+    nbr = torch.empty((m, max(k, 0)), device=dev, dtype=torch.int32)
+    d2 = torch.empty((m, max(k, 0)), device=dev, dtype=torch.float64) if return_d2 else None
+    visits = torch.empty(m, device=dev, dtype=torch.int32) if return_visits else None
+    _abi("mdf_pts_knn", (index.buf.data_ptr(), index.n, index.nbytes, qidx, q.data_ptr() if q is not None and m else None, m, qbytes, k,
+                         nbr.data_ptr() if m else None, d2.data_ptr() if return_d2 and m else None,
+                         visits.data_ptr() if return_visits and m else None, _stream(nbr)),
+         tag=f"n{index.n} m{m} k{k}", work={"queries": float(m), "bound": "valu"})
+    return nbr if not (return_d2 or return_visits) else (nbr,) + ((d2,) if return_d2 else ()) + ((visits,) if return_visits else ())
+
+
+def estimate_normals(pts_or_index, dirs=None, k=30, return_cov=False):
+    """Normals of a point cloud from its k nearest neighbours (mdf_pts_normals; the point itself is one of them): -> normals [n,3]
+    fp64 on the GPU in input order, the unit eigenvector of the neighbours' covariance for its smallest eigenvalue, (0, 0, 1)
+    when min(k, n) < 3.  dirs [n,3] (fp32) orients them: a normal n is kept when ((nx*dx) + ny*dy) + nz*dz > 0 and negated
+    otherwise.  pts_or_index: GPU [n,3] or a PointIndex.  return_cov appends the covariance [n,6] (xx, xy, xz, yy, yz, zz), whose
+    sums run over the neighbours in knn_search's order.  The neighbour lists are never stored."""
+    index = pts_or_index if isinstance(pts_or_index, PointIndex) else point_index(pts_or_index)
+    n, dev = index.n, index.device
+    if dirs is not None:
+        _need_gpu(dirs)
+        dirs = _f32c(dirs).reshape(-1, 3)
+        if dirs.shape[0] != n:
+            raise ValueError(f"estimate_normals: {dirs.shape[0]} dirs for {n} points")
+    nrm = torch.empty((n, 3), device=dev, dtype=torch.float64)
+    cov = torch.empty((n, 6), device=dev, dtype=torch.float64) if return_cov else None
+    _abi("mdf_pts_normals", (index.buf.data_ptr(), n, index.nbytes, int(k), dirs.data_ptr() if dirs is not None and n else None,
+                             nrm.data_ptr() if n else None, cov.data_ptr() if return_cov and n else None, _stream(nrm)),
+         tag=f"n{n} k{int(k)}", work={"queries": float(n), "bound": "valu"})
+    return (nrm, cov) if return_cov else nrm
+
+
+def nn_spacing(index):
+    """The distance from every point of the index to its nearest other point (Open3D's compute_nearest_neighbor_distance): the
+    square root of the second entry of a k = 2 self-query, so 0 for a duplicated point (and +inf for a lone point).  -> [n] fp64."""
+    if not isinstance(index, PointIndex):
+        raise TypeError("nn_spacing: index must come from point_index()")
+    _, d2 = knn_search(index, index, 2, return_d2=True)
+    return torch.sqrt(d2[:, 1])
 
 
 def transform_points(pts, T):

@@ -4,8 +4,11 @@ Per scan: the probability filter (prob > 0.8), the visibility filter, visibility
 the visibility filter and the small-segment filter run as ONE ops.pcd_fuse call with every view resident on the GPU
 (mdf_pcd_fuse_fwd), then the mask-true pixels are lifted to world points and written to {out}/{scan}.ply (or
 {eval}/{scan}/{filter}/{scan}.ply without -o).  Images are read with PIL and cropped top-left to the depth maps' size.
-Scans shard over ranks (one process per GPU, no collective).  Normal estimation and voxel downsampling are not available
-yet: run with --no_normal and without --downsample.
+Scans shard over ranks (one process per GPU, no collective).
+
+This entry point runs stages 1-6 only: main() refuses a call without --no_normal or with --downsample.  Normal estimation
+and voxel downsampling (stages 7 and 8, ops.pcd_fuse(normals=, downsample=)) run from tools/pcd/cloud.py, which takes the same
+arguments with the reference's defaults and shares build_parser(), run() and get_cloud() with this file.
 
   python mdf-net_amd/tools/pcd/fusion.py -r DATA_ROOT -e OUTPUTS -o PLY_DIR -d tanks -s intermediate --no_normal
 """
@@ -87,6 +90,7 @@ def get_cloud(dataset_root, scan, img_folder, cam_folder, eval_folder, args, dev
     out = ops.pcd_fuse(g(sc["depths"]), g(sc["probs"]), g(sc["images"]), sc["K"], sc["E"], sc["srcs"], view=args.view,
                        vthresh=args.vthresh, normals=not args.no_normal, downsample=args.downsample)
     xyz, rgb = out["xyz"].cpu().numpy(), out["rgb"].cpu().numpy()
+    nrm = out["normals"].cpu().numpy() if "normals" in out else None
     t2 = time.time()
     if args.write_mask:
         os.makedirs(os.path.join(eval_location, args.filter_folder), exist_ok=True)
@@ -98,18 +102,25 @@ def get_cloud(dataset_root, scan, img_folder, cam_folder, eval_folder, args, dev
     else:
         ply_path = os.path.join(args.outply_folder, scan + ".ply")
     os.makedirs(os.path.dirname(os.path.abspath(ply_path)), exist_ok=True)
-    write_ply(ply_path, xyz, rgb)
+    if nrm is not None:
+        write_ply(ply_path, xyz, rgb, normals=nrm)
+    else:
+        write_ply(ply_path, xyz, rgb)
+    if "voxel" in out:
+        fused = int(out["counts"].sum().item())
+        print(f"{scan}: downsampled {fused} -> {len(xyz)} points at voxel size {out['voxel']:.9g}")
     print(f"{scan}: {len(sc['ids'])} views, {len(xyz)} points (load {t1 - t0:.2f}s, fuse {t2 - t1:.2f}s) -> {ply_path}")
     return ply_path
 
 
-def main(argv=None):
+def build_parser():
     parser = argparse.ArgumentParser(description="point-cloud fusion with visibility and small-segment filters")
     parser.add_argument("--view", type=int, default=10)
     parser.add_argument("--vthresh", type=int, default=4)
     parser.add_argument("--cam_scale", type=float, default=1)
-    parser.add_argument("--downsample", type=float, default=None, help="(not implemented yet)")
-    parser.add_argument("--no_normal", action="store_true", default=False, help="required: normals are not implemented yet")
+    parser.add_argument("--downsample", type=float, default=None, help="voxel size, or -1 for the 90th percentile of the "
+                        "nearest-neighbour spacing (cloud.py only)")
+    parser.add_argument("--no_normal", action="store_true", default=False, help="skip normal estimation (required by fusion.py)")
     parser.add_argument("--write_mask", action="store_true", default=False)
     import config                       # the project's roots (MDF_DATA_ROOT, MDF_OUTPUT_ROOT), as eval.py writes them
     parser.add_argument("-r", "--root_folder", default=config.DATA_ROOT, type=str, help="dataset root location")
@@ -119,10 +130,11 @@ def main(argv=None):
     parser.add_argument("-s", "--set", default="intermediate", type=str, help="tanks set: intermediate or advanced")
     parser.add_argument("-f", "--filter_folder", default="filter", type=str, help="filter output location")
     parser.add_argument("--scans", default=None, type=str, help="comma-separated scans (DTU numbers or Tanks names)")
-    args = parser.parse_args(argv)
-    if not args.no_normal or args.downsample is not None:
-        raise SystemExit("normal estimation and voxel downsampling are not implemented yet: run with --no_normal and "
-                         "without --downsample")
+    return parser
+
+
+def run(args):
+    """Fuse every scan the arguments name (this rank's share) -> the PLY paths written."""
     if args.dataset == "dtu":
         dataset_root = os.path.join(args.root_folder, "dtu1600x1200")
         labels = [s.strip() for s in args.scans.split(",")] if args.scans else [str(x) for x in DTU_SCANS]
@@ -145,6 +157,14 @@ def main(argv=None):
         print("scan:", scans[i], "all time:", (time.time() - t0) / 60, "min")
     shard.barrier()
     return written
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if not args.no_normal or args.downsample is not None:
+        raise SystemExit("normal estimation and voxel downsampling are not implemented in fusion.py: run it with --no_normal "
+                         "and without --downsample, or run tools/pcd/cloud.py, which has both")
+    return run(args)
 
 
 if __name__ == "__main__":

@@ -4,7 +4,7 @@ at 1920 x 1056 with --views views (default 64) and 10 sources each.
 Times every stage with HIP events around its own mdf_pcd_fuse_fwd call (one step per call, the state carried between calls):
 the probability filter (torch), the three visibility filters, visibility fusion, average fusion, the small-segment filter,
 and the compaction.  Reports candidates/s of visibility fusion (N (V+1) H W candidate slots: every reference and source pixel,
-valid or not) and points/s of the compaction.  Normal estimation is not implemented, so there is no stage-7 rate.
+valid or not) and points/s of the compaction.  Stages 7 and 8 (normals, voxel downsampling) are timed by scripts/bench_pcd_normals.py.
   python scripts/bench_pcd_fusion.py [--views 64] [--repeats 3] [--out profiles/pcd_fusion_bench.json]"""
 import argparse
 import json
