@@ -213,8 +213,15 @@ int mdf_range_affine_fwd(const float* x, const float* lo, const float* span, int
  * mode 1 = gauss1 (depthhypos.py:169-215) with hypotheses shared by all pixels: `fit_row` is
  *          row 0 of (X^T X)^-1 X^T, [B,D], computed by the host with the reference's own torch
  *          calls (the 3x3 normal matrix has cond ~1e14 in fp32);
- * mode 2 = laplace (depthhypos.py:78-125), per-pixel or shared hypotheses.
- * Step 1: s [B,h,w].  Step 2: bilinear x2 upsample of s and depth (align_corners=False), range
+ * mode 2 = laplace (depthhypos.py:78-125), per-pixel or shared hypotheses;
+ * mode 3 = gauss0 (depthhypos.py:127-166), per-pixel or shared hypotheses; needs depth and hypos;
+ * mode 4 = gauss1 with per-pixel or shared hypotheses; needs hypos, `fit_row` is not used (may be
+ *          null).  Modes 3 and 4 fit centred regressors on the device and are held to the
+ *          reference's code in float64, not to its fp32 bits (its fp32 3x3 inverse is noise for
+ *          per-pixel hypotheses); a pixel with fewer than 2 distinct (x - depth)^2 (mode 3) or
+ *          fewer than 3 distinct hypotheses (mode 4) gets s = NaN.
+ * Step 1: s [B,h,w].  Step 2 (mode 1 for every Gaussian curve, 2 for laplace): bilinear x2
+ * upsample of s and depth (align_corners=False), range
  * from the curve, clamps, D_out hypotheses per pixel -> hypos_out [B,D_out,2h,2w].
  *   range [B,2] = (depth_min, depth_max) as float32;  log_thresh = f32 ln(prob_thresh), computed by
  *   the host with torch.log (depthhypos.py:55,57) so it carries the reference's rounding.          */

@@ -150,17 +150,44 @@ ngroups = (32, 16, 8)
 
 
 AGGREGATES = ("vector", "variance")
+CURVES = ("gauss0", "gauss1", "laplace")
 
 
-def build_model(aggregate="vector"):
-    """A fresh CoreNet.  aggregate="vector" (default): composed exactly like the reference's singleton.  aggregate="variance":
+def parse_pair(text, kind):
+    """ "gauss1,laplace" -> ("gauss1", "laplace");  "0.95,1e-5" with kind=float -> (0.95, 1e-05)  (train.py / eval.py flags)."""
+    parts = [p.strip() for p in text.split(",")]
+    if len(parts) != 2:
+        raise ValueError(f"expected two comma-separated values (stage 1, stage 2), got {text!r}")
+    return tuple(kind(p) for p in parts)
+
+
+def _curve_args(curves, thresh):
+    """-> per-stage (curve_calss, prob_thresh) lists of the three HyposByFit slots, checked."""
+    curves = tuple(curve_calss[1:]) if curves is None else tuple(curves)
+    thresh = tuple(prob_thresh[1:]) if thresh is None else tuple(thresh)
+    if len(curves) != 2 or any(c not in CURVES for c in curves):
+        raise ValueError(f"curves={curves!r}: a pair (stage 1, stage 2) out of {CURVES}")
+    if len(thresh) != 2:
+        raise ValueError(f"prob_thresh={thresh!r}: a pair (stage 1, stage 2)")
+    for c, t in zip(curves, thresh):
+        # the hypothesis range is sqrt(-s ln t) (Gaussian) or |s ln t| (Laplace): t must lie inside (0, 1)
+        if not 0.0 < float(t) < 1.0:
+            raise ValueError(f"prob_thresh={t!r} for curve {c!r}: the threshold must lie in (0, 1)")
+    return [None] + list(curves), [0.0] + [float(t) for t in thresh]
+
+
+def build_model(aggregate="vector", curves=None, prob_thresh=None):
+    """A fresh CoreNet.  curves: the curve HyposByFit fits before stages 1 and 2, default ("gauss1", "laplace"); prob_thresh: their
+    thresholds, default (0.95, 1e-5).  Every choice has the same state_dict (the slot has no parameters), so one checkpoint loads
+    into all of them; which curves it was trained with is the caller's to keep.  aggregate="vector" (default): composed exactly like the reference's singleton.  aggregate="variance":
     the classic MVSNet variance cost volume in the Homoaggre slots (homo_aggregate_by_variance, homoaggregate.py:49-69), whose
     cost volume has the C = 2 G feature channels, so the regularisers' first layers are 64->16, 32->8, 16->8.  That model has no
     `Homoaggre.*` parameters and differently shaped `Regular.{0,1,2}.conv01` first layers: reference checkpoints (and those of
     the vector model) do not load into it."""
     if aggregate not in AGGREGATES:
         raise ValueError(f"aggregate={aggregate!r}: choose one of {AGGREGATES}")
-    hypos = nn.ModuleList([HyposByFit(ndepths[i], curve_calss[i], prob_thresh[i]) for i in range(stages - 1)])
+    cv, th = _curve_args(curves, prob_thresh)
+    hypos = nn.ModuleList([HyposByFit(ndepths[i], cv[i], th[i]) for i in range(stages - 1)])
     if aggregate == "variance":
         from net.unit.homoaggregate import homo_aggregate_by_variance
         aggre = [homo_aggregate_by_variance] * (stages - 1)

@@ -1,9 +1,10 @@
 // Per-pixel heads between the stages: soft-argmin depth regression (net/unit/regress.py:5-7),
 // photometric confidence (regress.py:9-25) and the curve-fit hypothesis generator
-// (net/unit/depthhypos.py:27-125,169-215).  All are HBM-bound streaming kernels: one thread per
+// (net/unit/depthhypos.py:27-215).  All are HBM-bound streaming kernels: one thread per
 // pixel, the D axis walked with stride h*w so every load of a wavefront is one coalesced 256-B row.
 // The reference builds [B,h,w,D,3] temporaries and a batched 3x3 inverse for the gauss fit; here the
-// fit is a dot product with a host-prepared row (hypotheses are shared by all pixels at that stage).
+// fit is a dot product with a host-prepared row (hypotheses are shared by all pixels at that stage); gauss0 and gauss1 with
+// per-pixel hypotheses are centred fits in registers (hypos_curve_fit_kernel).
 #include "common.h"
 
 namespace {
@@ -152,6 +153,145 @@ __global__ void hypos_fit_kernel(int mode, const float* __restrict__ prob, const
   }
 }
 
+// ---- modes 3 and 4: the gauss0 fit and the gauss1 fit with hypotheses of either form (depthhypos.py:127-166, 169-215) ----
+// The reference inverts the normal matrix of the uncentred regressors per pixel; with hypotheses near 600 and a spread of
+// millimetres its fp32 result is noise (gauss1: median relative error 0.48 against its own code in float64).  These two modes
+// therefore do not mirror its bits: they compute the same least-squares slope from centred regressors, and are held to the
+// reference's code in float64 (tests/hypos_oracle.py has the operation order restated and the rounding count).
+//
+// Every sum runs in four interleaved accumulators: a dependent chain of D / 4 instead of D (one wave per SIMD: nothing else hides
+// the latency) and as many fewer roundings.  d & 3 is a constant in the unrolled forms.
+struct Sum4 {
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  __device__ __forceinline__ void fma(int d, float x, float y) {   // += x * y; add: y = 1 is exact
+    switch (d & 3) {
+      case 0: a0 = __fmaf_rn(x, y, a0); break;
+      case 1: a1 = __fmaf_rn(x, y, a1); break;
+      case 2: a2 = __fmaf_rn(x, y, a2); break;
+      default: a3 = __fmaf_rn(x, y, a3); break;
+    }
+  }
+  __device__ __forceinline__ void add(int d, float v) { fma(d, v, 1.0f); }
+  __device__ __forceinline__ float result() const { return (a0 + a1) + (a2 + a3); }
+};
+
+template <int DT> constexpr int kUnrollD = DT ? DT : 1;   // the register forms unroll fully, the generic form not at all
+
+// Mean, then corrected by the mean of the residuals: what is left is the rounding of the last addition, and D equal values give
+// exactly that value (the residuals are a rounding error of it, far below half an ulp), so a degenerate pixel centres to exact zeros.
+template <int DT, class V>
+__device__ __forceinline__ float mean_corrected(int D_rt, V v) {
+  const int D = DT ? DT : D_rt;
+  Sum4 s, r;
+#pragma unroll kUnrollD<DT>
+  for (int d = 0; d < D; ++d) s.add(d, v(d));
+  const float m1 = s.result() / (float)D;
+#pragma unroll kUnrollD<DT>
+  for (int d = 0; d < D; ++d) r.add(d, v(d) - m1);
+  return m1 + r.result() / (float)D;
+}
+
+// mode 3: z = b0 u + b1 with u = (x - depth)^2;  b0 = sum (u - mean u) z / sum (u - mean u)^2;  s = |-1 / b0| = |den / num|.
+// Fewer than two distinct u: every centred u is an exact zero and s = 0/0 = NaN (the reference's torch.inverse raises there).
+template <int DT, class U, class Z>
+__device__ __forceinline__ float gauss0_fit(int D_rt, U u, Z z) {
+  const int D = DT ? DT : D_rt;
+  const float um = mean_corrected<DT>(D_rt, u);
+  Sum4 num, den;
+#pragma unroll kUnrollD<DT>
+  for (int d = 0; d < D; ++d) {
+    const float c = u(d) - um;
+    num.fma(d, c, z(d));
+    den.fma(d, c, c);
+  }
+  return fabsf(den.result() / num.result());
+}
+
+// mode 4: z = b0 x^2 + b1 x + b2.  b0 does not change under a shift of x and scales by sigma^2 under x -> x / sigma, so the fit runs
+// in t = (x - mean x) * 2^-k, 2^k the power of two above max |x - mean x| (an exact scaling, |t| < 1), with the quadratic
+// orthogonalised against 1 and t: q = t^2 - alpha t - beta, (alpha, beta) from the 2x2 system in n, sum t, sum t^2, sum t^3;
+// b0 = sum q z / sum q^2 * 2^-2k;  s = |-1 / b0|.
+// Fewer than three distinct hypotheses (every x is the pixel's smallest or largest): q is identically zero there, rounding would
+// leave noise in its place, so both sums are set to that zero and s = 0/0 = NaN (the reference's torch.inverse raises there).
+template <int DT, class X, class Z>
+__device__ __forceinline__ float gauss1_fit(int D_rt, X x, Z z) {
+  const int D = DT ? DT : D_rt;
+  const float xm = mean_corrected<DT>(D_rt, x);
+  float lo = x(0), hi = lo, sig = 0.0f;
+#pragma unroll kUnrollD<DT>
+  for (int d = 0; d < D; ++d) {
+    const float v = x(d);
+    lo = fminf(lo, v);
+    hi = fmaxf(hi, v);
+    sig = fmaxf(sig, fabsf(v - xm));
+  }
+  bool three = false;
+#pragma unroll kUnrollD<DT>
+  for (int d = 0; d < D; ++d) three = three || (x(d) != lo && x(d) != hi);
+  int k;
+  frexpf(sig, &k);
+  Sum4 m1, m2, m3;
+#pragma unroll kUnrollD<DT>
+  for (int d = 0; d < D; ++d) {
+    const float t = ldexpf(x(d) - xm, -k), w = t * t;
+    m1.add(d, t);
+    m2.add(d, w);
+    m3.fma(d, w, t);
+  }
+  const float n = (float)D, s1 = m1.result(), s2 = m2.result(), s3 = m3.result();
+  const float det = __fmaf_rn(n, s2, -(s1 * s1));
+  const float alpha = __fmaf_rn(n, s3, -(s1 * s2)) / det;
+  const float beta = __fmaf_rn(s2, s2, -(s1 * s3)) / det;
+  Sum4 num, den;
+#pragma unroll kUnrollD<DT>
+  for (int d = 0; d < D; ++d) {
+    const float t = ldexpf(x(d) - xm, -k);
+    const float q = __fmaf_rn(t, t - alpha, -beta);
+    num.fma(d, q, z(d));
+    den.fma(d, q, q);
+  }
+  const float nu = three ? num.result() : 0.0f, de = three ? den.result() : 0.0f;
+  return fabsf(ldexpf(de / nu, 2 * k));
+}
+
+// mode 3: gauss0, mode 4: gauss1.  One thread per pixel; with D at compile time the D planes of prob and hypos are loaded into
+// registers first (plane stride h*w: coalesced rows) and every pass runs over registers; DT = 0 walks memory again in every pass.
+template <int DT>
+__global__ __launch_bounds__(kThreads) void hypos_curve_fit_kernel(int mode, const float* __restrict__ prob, const float* __restrict__ depth,
+                                       const float* __restrict__ hypos, int per_pixel, float* __restrict__ s_out, int B, int D_rt,
+                                       int hw) {
+  const int D = DT ? DT : D_rt;
+  const size_t n = (size_t)B * hw;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t b = i / hw, pix = i % hw;
+    const float* p = prob + b * D * hw + pix;
+    const float dep = mode == 3 ? depth[i] : 0.0f;
+    if constexpr (DT != 0) {
+      float zv[DT], xv[DT];
+#pragma unroll
+      for (int d = 0; d < DT; ++d) { zv[d] = p[(size_t)d * hw]; xv[d] = hyp_at(hypos, per_pixel, b, D, d, hw, pix); }
+#pragma unroll
+      for (int d = 0; d < DT; ++d) zv[d] = logf(fmaxf(zv[d], 1e-40f));
+      auto z = [&](int d) { return zv[d]; };
+      if (mode == 3) {
+#pragma unroll
+        for (int d = 0; d < DT; ++d) { const float e = xv[d] - dep; xv[d] = e * e; }
+        s_out[i] = gauss0_fit<DT>(D, [&](int d) { return xv[d]; }, z);
+      } else {
+        s_out[i] = gauss1_fit<DT>(D, [&](int d) { return xv[d]; }, z);
+      }
+    } else {
+      auto z = [&](int d) { return logf(fmaxf(p[(size_t)d * hw], 1e-40f)); };
+      auto x = [&](int d) { return hyp_at(hypos, per_pixel, b, D, d, hw, pix); };
+      if (mode == 3) {
+        s_out[i] = gauss0_fit<0>(D, [&](int d) { const float e = x(d) - dep; return e * e; }, z);
+      } else {
+        s_out[i] = gauss1_fit<0>(D, x, z);
+      }
+    }
+  }
+}
+
 // ATen upsample_bilinear2d, align_corners=False, scale 2: src = (o+0.5)*0.5-0.5 clamped at 0.
 __device__ __forceinline__ void up2_coord(int o, int n_in, int& i0, int& i1, float& l0, float& l1) {
   float src = ((float)o + 0.5f) * 0.5f - 0.5f;
@@ -275,8 +415,16 @@ extern "C" int mdf_hypos_fit_fwd(int mode, const float* prob, const float* depth
                                          "only after the uniform stage)");
   } else if (mode == 2) {
     MDF_REQUIRE(depth && hypos, "laplace fit needs depth and hypos");
+  } else if (mode == 3 || mode == 4) {
+    if (mode == 3) MDF_REQUIRE(depth && hypos, "gauss0 fit needs depth and hypos");
+    else MDF_REQUIRE(hypos, "gauss1 fit (mode 4) needs hypos");
+#define MDF_HC(DT) hipLaunchKernelGGL(hypos_curve_fit_kernel<DT>, dim3(grid_for((size_t)B * h * w)), dim3(block_for((size_t)B * h * w)), 0, (hipStream_t)stream, \
+                                      mode, prob, depth, hypos, hypos_per_pixel, s_out, B, D, h * w)
+    if (D == 48) MDF_HC(48); else if (D == 24) MDF_HC(24); else if (D == 8) MDF_HC(8); else MDF_HC(0);
+#undef MDF_HC
+    return mdf::check_launch("hypos_curve_fit_kernel");
   } else {
-    return mdf::fail(MDF_EARG, "mode must be 1 (gauss1) or 2 (laplace), got %d", mode);
+    return mdf::fail(MDF_EARG, "mode must be 1 (gauss1, shared hypotheses), 2 (laplace), 3 (gauss0) or 4 (gauss1), got %d", mode);
   }
 #define MDF_HF(DT) hipLaunchKernelGGL(hypos_fit_kernel<DT>, dim3(grid_for((size_t)B * h * w)), dim3(block_for((size_t)B * h * w)), 0, (hipStream_t)stream, mode, \
                                       prob, depth, hypos, hypos_per_pixel, fit_row, s_out, B, D, h * w)

@@ -104,6 +104,9 @@ def main():
     parser.add_argument("-s", "--set", default="intermediate", type=str, choices=["intermediate", "advanced"])
     parser.add_argument("--aggregate", default="vector", type=str, choices=list(config.AGGREGATES),
                         help="cost-volume operator the checkpoint was trained with (train.py --aggregate)")
+    parser.add_argument("--curves", default="gauss1,laplace", type=str,
+                        help="hypothesis curves the checkpoint was trained with (train.py --curves): two of gauss0, gauss1, laplace")
+    parser.add_argument("--prob_thresh", default="0.95,1e-5", type=str, help="their probability thresholds, each inside (0, 1)")
     args = parser.parse_args()
     logging.info(args)
     rank, world, local = shard.init()
@@ -116,7 +119,9 @@ def main():
         load_args, eval_args = config.LoadTanks(tanks_set=args.set), config.EvalTanks()
         from load.tankseval import LoadDataset
         dataset = LoadDataset(datasetpath=load_args.eval_root, scenelist=load_args.scenelist, nviews=eval_args.nviews)
-    model = config.model if args.aggregate == "vector" else config.build_model(aggregate=args.aggregate)
+    curves, thresh = config.parse_pair(args.curves, str), config.parse_pair(args.prob_thresh, float)
+    default = args.aggregate == "vector" and curves == tuple(config.curve_calss[1:]) and thresh == tuple(config.prob_thresh[1:])
+    model = config.model if default else config.build_model(aggregate=args.aggregate, curves=curves, prob_thresh=thresh)
     if args.pre_model is not None:
         model.load_state_dict(torch.load(args.pre_model, map_location="cpu")["model"])
     model.to(eval_args.DEVICE)

@@ -347,7 +347,13 @@ def gauss1_fit_row(depth_hypos):
 
 
 def hypos_fit(mode, prob, depth, depth_hypos, fit_row=None):
-    """Step 1 of HyposByFit: per-pixel curve parameter s [B,h,w].  mode 1 gauss1, 2 laplace."""
+    """Step 1 of HyposByFit: per-pixel curve parameter s [B,h,w].
+      mode 1  gauss1, hypotheses [B,D,1,1] only: needs `fit_row` (gauss1_fit_row); mirrors the reference's fp32 bits
+      mode 2  laplace: needs `depth`; hypotheses [B,D,1,1] or [B,D,h,w]
+      mode 3  gauss0: needs `depth`; hypotheses of either form
+      mode 4  gauss1, hypotheses of either form: needs neither `depth` nor `fit_row`
+    Modes 3 and 4 are centred fits held to the reference's code in float64 (its fp32 is noise for per-pixel hypotheses); a pixel
+    whose fit is not determined (fewer than 2 distinct (x - depth)^2, fewer than 3 distinct hypotheses) gets NaN."""
     _need_gpu(prob)
     b, d, h, w = prob.shape
     prob = _f32c(prob)

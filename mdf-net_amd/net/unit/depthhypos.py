@@ -4,17 +4,35 @@ import torch.nn as nn
 
 from mdfnet_hip import controlplane, hostmirror, layers, ops
 
-_MODES = {"gauss1": 1, "laplace": 2}
+CURVES = ("gauss0", "gauss1", "laplace")
+_STEP2 = {"gauss0": 1, "gauss1": 1, "laplace": 2}     # mdf_hypos_from_fit_fwd: sqrt(-s ln thr) for both Gaussians, |s ln thr|
+
+
+def fit_mode(curve, per_pixel):
+    """mdf_hypos_fit_fwd mode of a curve: gauss1 on hypotheses shared by all pixels keeps the path that mirrors the reference's
+    bits (mode 1, host-prepared fit row); gauss0 and per-pixel gauss1 are the centred device fits (modes 3, 4)."""
+    if curve == "gauss0":
+        return 3
+    if curve == "gauss1":
+        return 4 if per_pixel else 1
+    if curve == "laplace":
+        return 2
+    raise NotImplementedError(f"HyposByFit curve '{curve}' is not built ({', '.join(CURVES)} are)")
 
 
 class HyposByFit(nn.Module):
     """HyposByFit(ndepths, curve_calss, prob_thresh); no parameters or buffers (contributes nothing to
-    the state_dict, like the reference whose prob_thresh is a plain tensor attribute)."""
+    the state_dict, like the reference whose prob_thresh is a plain tensor attribute).
+
+    ops.recorded("log_thresh", step-2 mode) hands out the logarithms recorded for the pinned goldens of the default composition.
+    It is keyed by the step-2 mode, which two Gaussian stages with different thresholds would share, so only a slot with one of
+    the default composition's (curve, threshold) pairs consults it; every other takes log(prob_thresh)."""
 
     def __init__(self, ndepths: int = 16, curve_calss: str = "gauss1", prob_thresh: float = 0.95) -> None:
         super().__init__()
         self.ndepths, self.curve_calss = ndepths, curve_calss
         self.prob_thresh = torch.tensor(prob_thresh)
+        self.default_curve = (curve_calss, float(prob_thresh)) in (("gauss1", 0.95), ("laplace", 1e-5))     # config.py:147-148
 
     def uniform_host(self, depth_range):
         """depthhypos.py:31-38 on the host (B*D floats; GPU `tensor / int` rounds differently) -> [B,D,1,1] CPU."""
@@ -36,28 +54,23 @@ class HyposByFit(nn.Module):
     def forward(self, depth, depth_range, prob_volume, depth_hypos, upsample=False):
         if depth is None:
             return self._uniform(depth_range)
+        mode = fit_mode(self.curve_calss, depth_hypos.shape[-1] != 1 or depth_hypos.shape[-2] != 1)
         on_gpu = depth.is_cuda and prob_volume.is_cuda      # no gradient flows here (depthhypos.py:40): same kernels in training
         if not on_gpu and not layers.use_hip(self, depth.detach(), prob_volume.detach()):
-            if self.curve_calss not in _MODES:
-                raise NotImplementedError(f"HyposByFit curve '{self.curve_calss}' is not built (gauss1, laplace are)")
             return layers.stock().hypos_by_fit(self.curve_calss, self.prob_thresh, self.ndepths, depth.detach(), depth_range,
                                          prob_volume.detach(), depth_hypos.detach(), upsample)
-        mode = _MODES.get(self.curve_calss)
-        if mode is None:
-            raise NotImplementedError(f"HyposByFit curve '{self.curve_calss}' is not built (gauss1, laplace are)")
+        step2 = _STEP2[self.curve_calss]
         with torch.no_grad():
             row = None
             plan = controlplane.for_range(depth_range)
             if mode == 1:
-                if depth_hypos.shape[-1] != 1:
-                    raise NotImplementedError("gauss1 fit needs hypotheses shared by all pixels ([B,D,1,1])")
                 if plan is not None and plan.fit_row is not None and depth_hypos is plan.hyp0:
                     row = plan.fit_row
                 else:
                     row = ops.gauss1_fit_row(hostmirror.get(depth_hypos)).to(depth.device, non_blocking=True)
             s = ops.hypos_fit(mode, prob_volume, depth, depth_hypos, row)
             rng = plan.rng if plan is not None else hostmirror.get(depth_range).float().contiguous().to(depth.device, non_blocking=True)
-            log_thr = ops.recorded("log_thresh", mode)
+            log_thr = ops.recorded("log_thresh", step2) if self.default_curve else None
             if log_thr is None:
                 log_thr = float(torch.log(self.prob_thresh))
-            return ops.hypos_from_fit(mode, s, depth, rng, log_thr, self.ndepths, bool(upsample))
+            return ops.hypos_from_fit(step2, s, depth, rng, log_thr, self.ndepths, bool(upsample))

@@ -80,17 +80,72 @@ def _fit_laplace(depth, prob, hypos):
     return 1 / torch.abs(torch.sum(x * y, dim=-1) / torch.sum(x * x, dim=-1))
 
 
+def _sum4(terms):
+    """Sum over dim 1 as four interleaved partial sums, (a0 + a1) + (a2 + a3): the grouping of hypos_fit modes 3 and 4 (each partial
+    sum in torch's own order)."""
+    a = [terms[:, k::4].sum(1) if k < terms.shape[1] else torch.zeros_like(terms[:, 0]) for k in range(4)]
+    return (a[0] + a[1]) + (a[2] + a[3])
+
+
+def _mean_corrected(v):
+    """Mean over dim 1, corrected by the mean of the residuals (equal values give exactly that value)."""
+    d = v.shape[1]
+    m1 = _sum4(v) / d
+    return m1 + _sum4(v - m1.unsqueeze(1)) / d
+
+
+def _fit_gauss0(depth, prob, hypos):
+    """depthhypos.py:127-166 as a centred fit: z = b0 u + b1, u = (x - depth)^2; s = |-1 / b0|.  The reference's code in float64
+    is the yardstick (tests/hypos_oracle.py), not its fp32 bits.  Fewer than two distinct u: 0/0 = NaN."""
+    z = torch.log(prob.clamp(min=1e-40))
+    u = (hypos - depth.unsqueeze(1)).expand_as(prob) ** 2
+    c = u - _mean_corrected(u).unsqueeze(1)
+    return torch.abs(_sum4(c * c) / _sum4(c * z))
+
+
+def _fit_gauss1_centred(prob, hypos):
+    """depthhypos.py:169-215 for hypotheses of either form, as hypos_fit mode 4 computes it: t = (x - mean x) * 2^-k, the quadratic
+    orthogonalised against 1 and t, b0 = sum q z / sum q^2 * 2^-2k; s = |-1 / b0|.  The reference's fp32 3x3 inverse is noise for
+    per-pixel hypotheses; its code in float64 is the yardstick.  Fewer than three distinct hypotheses: 0/0 = NaN."""
+    z = torch.log(prob.clamp(min=1e-40))
+    x = hypos.expand_as(prob)
+    n = x.shape[1]
+    e = x - _mean_corrected(x).unsqueeze(1)
+    lo, hi = x.min(1, keepdim=True).values, x.max(1, keepdim=True).values
+    three = ((x != lo) & (x != hi)).any(1)
+    k = torch.frexp(e.abs().max(1).values).exponent
+    t = torch.ldexp(e, -k.unsqueeze(1))
+    w = t * t
+    s1, s2, s3 = _sum4(t), _sum4(w), _sum4(w * t)
+    det = n * s2 - s1 * s1
+    alpha, beta = (n * s3 - s1 * s2) / det, (s2 * s2 - s1 * s3) / det
+    q = t * (t - alpha.unsqueeze(1)) - beta.unsqueeze(1)
+    zero = torch.zeros_like(s1)
+    num, den = torch.where(three, _sum4(q * z), zero), torch.where(three, _sum4(q * q), zero)
+    return torch.abs(torch.ldexp(den / num, 2 * k))
+
+
+def _fit(curve, depth, prob, hypos):
+    if curve == "gauss0":
+        return _fit_gauss0(depth, prob, hypos)
+    if curve == "gauss1":       # hypotheses shared by all pixels: the reference's own arithmetic, as the GPU path's mode 1 mirrors it
+        return _fit_gauss1(prob, hypos) if hypos.shape[-1] == 1 and hypos.shape[-2] == 1 else _fit_gauss1_centred(prob, hypos)
+    if curve == "laplace":
+        return _fit_laplace(depth, prob, hypos)
+    raise NotImplementedError(f"HyposByFit curve '{curve}' is not built (gauss0, gauss1, laplace are)")
+
+
 def hypos_by_fit(curve, prob_thresh, ndepths, depth, depth_range, prob, hypos, upsample):
     """HyposByFit.forward for depth is not None (always under no_grad in the reference, depthhypos.py:40)."""
     b = depth_range.shape[0]
     lo, hi = depth_range[:, 0].float(), depth_range[:, 1].float()
     with torch.no_grad():
-        s = _fit_gauss1(prob, hypos) if curve == "gauss1" else _fit_laplace(depth, prob, hypos)
+        s = _fit(curve, depth, prob, hypos)
         if upsample:
             s = F.interpolate(s.unsqueeze(1), scale_factor=2, mode="bilinear").squeeze(1)
             depth = F.interpolate(depth.unsqueeze(1), scale_factor=2, mode="bilinear").squeeze(1)
         thr = prob_thresh.to(s.device)
-        res = torch.sqrt(-1 * s * torch.log(thr)) if curve == "gauss1" else torch.abs(s * torch.log(thr))
+        res = torch.sqrt(-1 * s * torch.log(thr)) if curve in ("gauss0", "gauss1") else torch.abs(s * torch.log(thr))
         res = res.clamp(min=1e-6, max=(hi.max() - lo.min()) / 2)
         res = torch.minimum(res, ((hi - lo) * 0.2).reshape(b, 1, 1))
         step = res / (ndepths - 1)

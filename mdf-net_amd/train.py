@@ -74,6 +74,9 @@ def main():
     parser.add_argument("-l", "--cmd_label", default="", type=str)
     parser.add_argument("--aggregate", default="vector", type=str, choices=list(config.AGGREGATES),
                         help="cost-volume operator of the Homoaggre slots: the reference's VectorAggregate, or the variance cost volume")
+    parser.add_argument("--curves", default="gauss1,laplace", type=str,
+                        help="hypothesis curves fitted before stages 1 and 2: two of gauss0, gauss1, laplace")
+    parser.add_argument("--prob_thresh", default="0.95,1e-5", type=str, help="their probability thresholds, each inside (0, 1)")
     args = parser.parse_args()
     rank, world, local = shard.init()
     if args.dataset == "dtu":
@@ -87,7 +90,9 @@ def main():
         from load.blendedtrain import LoadDataset
         dataset = LoadDataset(datasetpath=load_args.train_root, nviews=train_args.nviews, robust_train=train_args.robust)
     device = train_args.DEVICE
-    model = config.model if args.aggregate == "vector" else config.build_model(aggregate=args.aggregate)
+    curves, thresh = config.parse_pair(args.curves, str), config.parse_pair(args.prob_thresh, float)
+    default = args.aggregate == "vector" and curves == tuple(config.curve_calss[1:]) and thresh == tuple(config.prob_thresh[1:])
+    model = config.model if default else config.build_model(aggregate=args.aggregate, curves=curves, prob_thresh=thresh)
     start_epoch = train_args.start_epoch
     if args.pre_model is not None:
         ckpt = torch.load(args.pre_model, map_location="cpu")
