@@ -11,6 +11,7 @@
 // ((m0*x0 + m1*x1) + m2*x2) [+ m3]; divides and the square root are IEEE-rounded; no fma (the library builds with
 // -ffp-contract=off).  Bilinear weights are exact fp32 (a texture unit quantises them to 8 fractional bits: DESIGN.md 7).
 #include "common.h"
+#include "scan_common.h"
 
 namespace {
 
@@ -123,39 +124,11 @@ __global__ __launch_bounds__(kBlock) void consensus_fuse_kernel(const FuseArgs p
   if (threadIdx.x == 0) p.block_counts[r * p.nblk + blockIdx.x] = kept;
 }
 
-// Exclusive scan of nitems block counts in one block (entries are split into contiguous chunks, one per thread).
-constexpr int kScanThreads = 1024;
-
-__global__ __launch_bounds__(kScanThreads) void consensus_scan_kernel(const int* __restrict__ counts, long long* __restrict__ offsets,
+// Exclusive scan of the nitems block counts, per-view counts and the total, in one block.
+__global__ __launch_bounds__(mdf::kScanThreads) void consensus_scan_kernel(const int* __restrict__ counts, long long* __restrict__ offsets,
                                                                       int nitems, int nblk, int n, int* __restrict__ view_counts,
                                                                       long long* __restrict__ total) {
-  __shared__ long long part[kScanThreads];
-  const int t = threadIdx.x;
-  const int chunk = (nitems + kScanThreads - 1) / kScanThreads;
-  const int lo = min(nitems, t * chunk), hi = min(nitems, lo + chunk);
-  long long s = 0;
-  for (int i = lo; i < hi; ++i) s += counts[i];
-  part[t] = s;
-  __syncthreads();
-  for (int off = 1; off < kScanThreads; off <<= 1) {     // Hillis-Steele inclusive scan of the chunk sums
-    const long long add = t >= off ? part[t - off] : 0;
-    __syncthreads();
-    part[t] += add;
-    __syncthreads();
-  }
-  long long run = part[t] - s;
-  for (int i = lo; i < hi; ++i) {
-    offsets[i] = run;
-    run += counts[i];
-  }
-  __threadfence_block();
-  __syncthreads();
-  const long long all = part[kScanThreads - 1];
-  for (int v = t; v < n; v += kScanThreads) {
-    const long long a = offsets[(size_t)v * nblk], b = v + 1 < n ? offsets[(size_t)(v + 1) * nblk] : all;
-    view_counts[v] = (int)(b - a);
-  }
-  if (t == 0) *total = all;
+  mdf::block_exclusive_scan<int, true>(counts, nitems, offsets, total, nblk, n, view_counts);
 }
 
 __global__ __launch_bounds__(kBlock) void consensus_compact_kernel(const float4* __restrict__ dense, const long long* __restrict__ offsets,
@@ -250,7 +223,7 @@ extern "C" int mdf_consensus_fuse_fwd(const float* depths, const unsigned char* 
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(consensus_fuse_kernel, dim3(L.nblk, n), dim3(kBlock), 0, s, p);
   if (int rc = mdf::check_launch("consensus_fuse_kernel")) return rc;
-  hipLaunchKernelGGL(consensus_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, L.counts, L.offsets, L.items, L.nblk, n,
+  hipLaunchKernelGGL(consensus_scan_kernel, dim3(1), dim3(mdf::kScanThreads), 0, s, L.counts, L.offsets, L.items, L.nblk, n,
                      view_counts, total);
   if (int rc = mdf::check_launch("consensus_scan_kernel")) return rc;
   if (xyz == nullptr) return MDF_OK;                 // two-phase use: the caller sizes the output from *total, then compacts

@@ -23,12 +23,13 @@
 // ((m0*x0 + m1*x1) + m2*x2) [+ m3*x3], every divide is IEEE, the reference's +1e-9 denominators are kept, the one square root
 // goes through double; the library builds with -ffp-contract=off.
 #include "common.h"
+#include "scan_common.h"
 
 namespace {
 
 constexpr int kCam = 64;      // floats per view in the camera table: K[9], K^-1[9], E[16], E^-1[16], centre[3], pad
 constexpr int kK = 0, kKi = 9, kE = 18, kEi = 34, kCtr = 50;
-constexpr int kBlock = 256;
+constexpr int kBlock = mdf::kScanBlock;     // 256: pcd_bin_sum_kernel / pcd_bin_offsets_kernel run scan_common.h's block bodies
 constexpr int kVis = 0, kAve = 1;
 constexpr int kSegWin = 4;
 constexpr int kBigBin = 256;     // bins above this many candidates are ranked by a whole block
@@ -406,42 +407,11 @@ __global__ __launch_bounds__(kBlock) void pcd_count_kernel(const unsigned char* 
   if (threadIdx.x == 0) counts[blockIdx.y * nblk + blockIdx.x] = kept;
 }
 
-// Exclusive scan of nitems counts in one block (contiguous chunks, one per thread).  With nblk > 0, view v's total is the sum
-// of items [v*nblk, (v+1)*nblk).
-constexpr int kScanThreads = 1024;
-
-__global__ __launch_bounds__(kScanThreads) void pcd_scan_kernel(const int* __restrict__ counts, long long* __restrict__ offsets,
+// Exclusive scan of nitems counts in one block.  With nblk > 0, view v's total is the sum of items [v*nblk, (v+1)*nblk).
+__global__ __launch_bounds__(mdf::kScanThreads) void pcd_scan_kernel(const int* __restrict__ counts, long long* __restrict__ offsets,
                                                                 int nitems, int nblk, int n, int* __restrict__ view_counts,
                                                                 long long* __restrict__ total) {
-  __shared__ long long part[kScanThreads];
-  const int t = threadIdx.x;
-  const int chunk = (nitems + kScanThreads - 1) / kScanThreads;
-  const int lo = min(nitems, t * chunk), hi = min(nitems, lo + chunk);
-  long long s = 0;
-  for (int i = lo; i < hi; ++i) s += counts[i];
-  part[t] = s;
-  __syncthreads();
-  for (int off = 1; off < kScanThreads; off <<= 1) {
-    const long long add = t >= off ? part[t - off] : 0;
-    __syncthreads();
-    part[t] += add;
-    __syncthreads();
-  }
-  long long run = part[t] - s;
-  for (int i = lo; i < hi; ++i) {
-    offsets[i] = run;
-    run += counts[i];
-  }
-  __threadfence_block();
-  __syncthreads();
-  const long long all = part[kScanThreads - 1];
-  if (view_counts != nullptr) {
-    for (int v = t; v < n; v += kScanThreads) {
-      const long long a = offsets[(size_t)v * nblk], b = v + 1 < n ? offsets[(size_t)(v + 1) * nblk] : all;
-      view_counts[v] = (int)(b - a);
-    }
-  }
-  if (t == 0 && total != nullptr) *total = all;
+  mdf::block_exclusive_scan<int, true>(counts, nitems, offsets, total, nblk, n, view_counts);
 }
 
 // Bin offsets of one reference view, a three-pass scan over many blocks (one block walking 2M counts in sequence took ~4.4 ms
@@ -450,23 +420,16 @@ __global__ __launch_bounds__(kScanThreads) void pcd_scan_kernel(const int* __res
 constexpr int kBinPer = 4, kBinChunk = kBlock * kBinPer;
 
 __global__ __launch_bounds__(kBlock) void pcd_bin_sum_kernel(const int* __restrict__ counts, int n, int* __restrict__ sums) {
-  __shared__ int part[kBlock];
   const int base = blockIdx.x * kBinChunk + threadIdx.x * kBinPer;
   int t = 0;
   for (int k = 0; k < kBinPer; ++k) t += base + k < n ? counts[base + k] : 0;
-  part[threadIdx.x] = t;
-  __syncthreads();
-  for (int off = kBlock / 2; off > 0; off >>= 1) {
-    if (threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) sums[blockIdx.x] = part[0];
+  const int sum = mdf::block_sum(t);
+  if (threadIdx.x == 0) sums[blockIdx.x] = sum;
 }
 
 __global__ __launch_bounds__(kBlock) void pcd_bin_offsets_kernel(const int* __restrict__ counts, int n,
                                                                  const long long* __restrict__ chunk_off,
                                                                  long long* __restrict__ offsets) {
-  __shared__ int part[kBlock];
   const int base = blockIdx.x * kBinChunk + threadIdx.x * kBinPer;
   int c[kBinPer];
   int t = 0;
@@ -474,15 +437,7 @@ __global__ __launch_bounds__(kBlock) void pcd_bin_offsets_kernel(const int* __re
     c[k] = base + k < n ? counts[base + k] : 0;
     t += c[k];
   }
-  part[threadIdx.x] = t;
-  __syncthreads();
-  for (int off = 1; off < kBlock; off <<= 1) {           // Hillis-Steele inclusive scan of the thread sums
-    const int add = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-    __syncthreads();
-    part[threadIdx.x] += add;
-    __syncthreads();
-  }
-  long long run = chunk_off[blockIdx.x] + (part[threadIdx.x] - t);
+  long long run = chunk_off[blockIdx.x] + (mdf::block_inclusive_scan(t) - t);
   for (int k = 0; k < kBinPer; ++k) {
     if (base + k < n) offsets[base + k] = run;
     run += c[k];
@@ -598,7 +553,7 @@ int run_fusion(const StepArgs& sp, const WsLayout& L, hipStream_t s) {
     if (int rc = mdf::check_launch("pcd_cand_count_kernel")) return rc;
     hipLaunchKernelGGL(pcd_bin_sum_kernel, dim3(L.nchunk), dim3(kBlock), 0, s, L.bin_count, L.hw, L.chunk_sums);
     if (int rc = mdf::check_launch("pcd_bin_sum_kernel")) return rc;
-    hipLaunchKernelGGL(pcd_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, L.chunk_sums, L.chunk_off, L.nchunk, 0, 0, nullptr, nullptr);
+    hipLaunchKernelGGL(pcd_scan_kernel, dim3(1), dim3(mdf::kScanThreads), 0, s, L.chunk_sums, L.chunk_off, L.nchunk, 0, 0, nullptr, nullptr);
     if (int rc = mdf::check_launch("pcd_scan_kernel")) return rc;
     hipLaunchKernelGGL(pcd_bin_offsets_kernel, dim3(L.nchunk), dim3(kBlock), 0, s, L.bin_count, L.hw, L.chunk_off, L.bin_off);
     if (int rc = mdf::check_launch("pcd_bin_offsets_kernel")) return rc;
@@ -665,7 +620,7 @@ extern "C" int mdf_pcd_fuse_fwd(float* depths, unsigned char* masks, const float
   }
   hipLaunchKernelGGL(pcd_count_kernel, grid, dim3(kBlock), 0, s, masks, L.hw, L.nblk, L.block_counts);
   if (int rc = mdf::check_launch("pcd_count_kernel")) return rc;
-  hipLaunchKernelGGL(pcd_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, L.block_counts, L.block_off, n * L.nblk, L.nblk, n,
+  hipLaunchKernelGGL(pcd_scan_kernel, dim3(1), dim3(mdf::kScanThreads), 0, s, L.block_counts, L.block_off, n * L.nblk, L.nblk, n,
                      view_counts, total);
   return mdf::check_launch("pcd_scan_kernel");
 }

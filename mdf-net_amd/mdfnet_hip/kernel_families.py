@@ -53,17 +53,19 @@ KERNEL_FAMILY = {
     "pcd_reproj_kernel": FILTER, "pcd_cand_count_kernel": FILTER, "pcd_cand_place_kernel": FILTER, "pcd_select_kernel": FILTER, "pcd_select_big_kernel": FILTER, "pcd_bin_sum_kernel": FILTER, "pcd_bin_offsets_kernel": FILTER,
     "pcd_seg_init_kernel": FILTER, "pcd_seg_hook_kernel": FILTER, "pcd_seg_count_kernel": FILTER, "pcd_seg_apply_kernel": FILTER,
     "pcd_count_kernel": FILTER, "pcd_scan_kernel": FILTER, "pcd_compact_kernel": FILTER,
-    # point_eval.hip (DTU evaluation: the MATLAB scorer's reducePts_haa / MaxDistCP / masks)
+    # point_index.hip (the spatial index, and the bounding box, radix sort and scan every point file shares)
     "pts_bbox_kernel": POINT_EVAL, "pts_bbox_final_kernel": POINT_EVAL, "pts_morton_kernel": POINT_EVAL, "pts_sort_hist_kernel": POINT_EVAL,
     "pts_sort_scan_kernel": POINT_EVAL, "pts_sort_scatter_kernel": POINT_EVAL, "pts_gather_kernel": POINT_EVAL, "pts_leaf_kernel": POINT_EVAL,
-    "pts_node_kernel": POINT_EVAL, "pts_nn_kernel": POINT_EVAL, "pts_rank_kernel": POINT_EVAL, "pts_radius_kernel": POINT_EVAL,
+    "pts_node_kernel": POINT_EVAL,
+    # point_eval.hip (DTU evaluation: the MATLAB scorer's reducePts_haa / MaxDistCP / masks)
+    "pts_nn_kernel": POINT_EVAL, "pts_rank_kernel": POINT_EVAL, "pts_radius_kernel": POINT_EVAL,
     "pts_reduce_init_kernel": POINT_EVAL, "pts_reduce_round_kernel": POINT_EVAL, "pts_reduce_step_kernel": POINT_EVAL,
     "pts_reduce_keep_kernel": POINT_EVAL, "pts_dtu_masks_kernel": POINT_EVAL,
-    # point_eval.hip (Tanks and Temples evaluation: nearest index, transform, crop volume, voxel grid, ICP sums)
+    # point_register.hip (Tanks and Temples evaluation: nearest index, transform, crop volume, voxel grid, ICP sums)
     "pts_nn_idx_kernel": POINT_EVAL, "pts_transform_kernel": POINT_EVAL, "pts_crop_kernel": POINT_EVAL, "pts_vox_key_kernel": POINT_EVAL,
     "pts_vox_chunk_sum_kernel": POINT_EVAL, "pts_vox_offsets_kernel": POINT_EVAL, "pts_vox_mean_kernel": POINT_EVAL,
     "pts_icp_moment_kernel": POINT_EVAL, "pts_icp_final_kernel": POINT_EVAL,
-    # point_eval.hip (point-cloud post-processing: k nearest neighbours, normal estimation)
+    # point_knn.hip (point-cloud post-processing: k nearest neighbours, normal estimation)
     "pts_knn_kernel": POINT_EVAL, "pts_normals_kernel": POINT_EVAL,
     # loss.hip
     "masked_smooth_l1_reduce_kernel": CONTROL, "masked_smooth_l1_finalize_kernel": CONTROL, "masked_smooth_l1_bwd_kernel": CONTROL,

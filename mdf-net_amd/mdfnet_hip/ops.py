@@ -982,6 +982,15 @@ def _host_doubles(vals, k):
     return (ctypes.c_double * k)(*a.tolist())
 
 
+def _queries_arg(queries):
+    """queries of a search, a PointIndex or GPU [m,3] -> (m, the index's pointer or None, the fp64 array or None, the index's bytes)."""
+    if isinstance(queries, PointIndex):
+        return queries.n, queries.buf.data_ptr(), None, queries.nbytes
+    _need_gpu(queries)
+    q = _pts64(queries)
+    return q.shape[0], None, q, 0
+
+
 def nn_distance(index, queries, bb=None, cap=DTU_MAX_DIST_CP, return_visits=False):
     """MaxDistCP(Qto = index's points, Qfrom = queries, BB, cap) of the DTU scorer (MaxDistCP.m): for every query the exact
     nearest-neighbour distance if it is < cap and the query lies in BB's cubes of side cap, else cap.  queries: GPU [m,3] (fp64)
@@ -990,17 +999,13 @@ def nn_distance(index, queries, bb=None, cap=DTU_MAX_DIST_CP, return_visits=Fals
     return_visits)."""
     if not isinstance(index, PointIndex):
         raise TypeError("nn_distance: index must come from point_index()")
-    if isinstance(queries, PointIndex):
-        m, qidx, qpts, qbytes = queries.n, queries.buf.data_ptr(), None, queries.nbytes
-    else:
-        _need_gpu(queries)
-        q = _pts64(queries)
-        m, qidx, qpts, qbytes = q.shape[0], None, q.data_ptr(), 0
+    m, qidx, q, qbytes = _queries_arg(queries)
     dev = index.device
     dist = torch.empty(m, device=dev, dtype=torch.float64)
     visits = torch.empty(m, device=dev, dtype=torch.int32) if return_visits else None
     bbh = _host_doubles(bb, 6) if bb is not None else None
     if m:
+        qpts = q.data_ptr() if q is not None else None
         _abi("mdf_pts_nn_dist", (index.buf.data_ptr(), index.n, index.nbytes, qidx, qpts, m, qbytes, bbh, float(cap), dist.data_ptr(),
                                  visits.data_ptr() if visits is not None else None, _stream(dist)),
              tag=f"n{index.n} m{m}", work={"queries": float(m), "bound": "valu"})
@@ -1161,18 +1166,14 @@ def nn_search(index, queries, cap, return_d2=False, return_visits=False):
     input positions).  return_d2 appends d^2 (+inf when none), return_visits the leaves visited per query."""
     if not isinstance(index, PointIndex):
         raise TypeError("nn_search: index must come from point_index()")
-    if isinstance(queries, PointIndex):
-        m, qidx, qpts, qbytes = queries.n, queries.buf.data_ptr(), None, queries.nbytes
-    else:
-        _need_gpu(queries)
-        q = _pts64(queries)
-        m, qidx, qpts, qbytes = q.shape[0], None, q.data_ptr(), 0
+    m, qidx, q, qbytes = _queries_arg(queries)
     dev = index.device
     dist = torch.empty(m, device=dev, dtype=torch.float64)
     d2 = torch.empty(m, device=dev, dtype=torch.float64) if return_d2 else None
     nearest = torch.empty(m, device=dev, dtype=torch.int32)
     visits = torch.empty(m, device=dev, dtype=torch.int32) if return_visits else None
     if m:
+        qpts = q.data_ptr() if q is not None else None
         _abi("mdf_pts_nn", (index.buf.data_ptr(), index.n, index.nbytes, qidx, qpts, m, qbytes, ctypes.c_double(float(cap)),
                             dist.data_ptr(), d2.data_ptr() if return_d2 else None, nearest.data_ptr(),
                             visits.data_ptr() if return_visits else None, _stream(dist)),
@@ -1181,14 +1182,6 @@ def nn_search(index, queries, cap, return_d2=False, return_visits=False):
 
 
 KNN_MAX = 32                   # MDF_PTS_KNN_MAX
-
-
-def _queries_arg(queries):
-    if isinstance(queries, PointIndex):
-        return queries.n, queries.buf.data_ptr(), None, queries.nbytes
-    _need_gpu(queries)
-    q = _pts64(queries)
-    return q.shape[0], None, q, 0
 
 
 def knn_search(index, queries, k, return_d2=False, return_visits=False):
