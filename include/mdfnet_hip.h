@@ -523,9 +523,13 @@ int mdf_upsample2_bilinear_bwd(const float* dfine, float* dcoarse, int B, int h,
 
 /* ---- backward of the `prob` head: softmax over D + soft-argmin (regular.py:69/133, regress.py:5-7), and the input
  *      gradient of its Conv3d(C->1,k3,p1).   dlogit [B,D,h,w]; ddepth [B,h,w] and/or dprob [B,D,h,w] (either may be
- *      NULL); w torch [1,C,3,3,3]; dx NDHWC [B,D,h,w,C], C in {8,16}.                                           */
+ *      NULL); w torch [1,C,3,3,3]; dx NDHWC [B,D,h,w,C], C in {8,16}.  hypos is read only when ddepth is given and
+ *      may be NULL without it.                                                                                   */
 int mdf_prob_softmax_regress_bwd(const float* prob, const float* hypos, int hypos_per_pixel, const float* ddepth,
                                  const float* dprob, float* dlogit, int B, int D, int h, int w, void* stream);
+/*      Read-only: the threads that share a pixel (1, 2, 4 or 8) in the launch above for this shape (< 0: error code).
+ *      Launches nothing.                                                                                          */
+int mdf_prob_softmax_regress_bwd_split(int B, int D, int h, int w);
 int mdf_prob_conv_dgrad(const float* dlogit, const float* w, float* dx, int B, int D, int h, int wd, int C, void* stream);
 /*      The same with the BatchNorm-backward sums of the regulariser's last layer taken on the way (dx is that layer's complete dz):
  *      stat_y = the layer's raw conv output [B*D*h*wd][C], stat_aux = its (a, b, mean, invstd) [4C] as mdf_bn_finalize_fwd wrote them,

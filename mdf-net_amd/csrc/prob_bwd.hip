@@ -63,6 +63,34 @@ __global__ __launch_bounds__(256) void softmax_regress_bwd_kernel(const float* _
   }
 }
 
+// The same without ddepth: g[d] = dprob[d] alone, so dlogit[d] = p[d] * (dp[d] - sum_k p[k] dp[k]) and the hypotheses are not part of the
+// gradient -- they may be NULL and are never read.  Same thread layout and the same order of the per-pixel sum as above.
+template <int S>
+__global__ __launch_bounds__(256) void softmax_bwd_dprob_kernel(const float* __restrict__ prob, const float* __restrict__ dprob,
+                                                                float* __restrict__ dlogit, int B, int D, int hw) {
+  constexpr int PPB = 256 / S;
+  __shared__ float part[S][PPB];
+  const int s = threadIdx.x / PPB, pl = threadIdx.x % PPB;
+  const long long i = (long long)blockIdx.x * PPB + pl;
+  const bool live = i < (long long)B * hw;
+  const long long ii = live ? i : 0;
+  const long long base = (ii / hw) * D * hw + ii % hw;
+  const float* pr = prob + base;
+  const float* dp = dprob + base;
+  float mp = 0.0f;
+  for (int d = s; d < D; d += S) mp = fmaf(pr[(long long)d * hw], dp[(long long)d * hw], mp);
+  if constexpr (S > 1) {
+    part[s][pl] = mp;
+    __syncthreads();
+    mp = 0.0f;
+#pragma unroll
+    for (int k = 0; k < S; ++k) mp += part[k][pl];
+  }
+  if (!live) return;
+  float* o = dlogit + base;
+  for (int d = s; d < D; d += S) o[(long long)d * hw] = pr[(long long)d * hw] * (dp[(long long)d * hw] - mp);
+}
+
 template <int CTRL>
 __device__ __forceinline__ float dpp_row_shr(float v) {     // lane l reads lane l - n of its 16-lane row (0 where there is none)
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
@@ -168,20 +196,34 @@ __global__ __launch_bounds__(256) void prob_conv_dgrad_kernel(const float* __res
 
 }  // namespace
 
+// threads per pixel: enough blocks for the chip at the coarse stages (pixels x S >= ~256k threads), never more than the planes
+extern "C" int mdf_prob_softmax_regress_bwd_split(int B, int D, int h, int w) {
+  if (B <= 0 || D <= 0 || h <= 0 || w <= 0) return mdf::fail(MDF_EARG, "bad shape");
+  const long long n = (long long)B * h * w;
+  int S = 1;
+  while (S < 8 && n * S < 262144 && 2 * S <= D) S *= 2;
+  return S;
+}
+
 extern "C" int mdf_prob_softmax_regress_bwd(const float* prob, const float* hypos, int hypos_per_pixel, const float* ddepth,
                                             const float* dprob, float* dlogit, int B, int D, int h, int w, void* stream) {
   MDF_REQUIRE(prob && dlogit && (ddepth || dprob), "null pointer argument");
   MDF_REQUIRE(!ddepth || hypos, "ddepth needs the hypotheses");
   MDF_REQUIRE(B > 0 && D > 0 && h > 0 && w > 0, "bad shape");
   const long long n = (long long)B * h * w;
-  // threads per pixel: enough blocks for the chip at the coarse stages (pixels x S >= ~256k threads), never more than the planes
-  int S = 1;
-  while (S < 8 && n * S < 262144 && 2 * S <= D) S *= 2;
-#define MDF_SRB(SS) hipLaunchKernelGGL(softmax_regress_bwd_kernel<SS>, dim3((unsigned)((n + 256 / SS - 1) / (256 / SS))), dim3(256), 0, (hipStream_t)stream, \
-                                       prob, hypos, hypos_per_pixel, ddepth, dprob, dlogit, B, D, h * w)
+  const int S = mdf_prob_softmax_regress_bwd_split(B, D, h, w);
+#define MDF_SRB(SS)                                                                                                                       \
+  do {                                                                                                                                    \
+    const dim3 grid((unsigned)((n + 256 / SS - 1) / (256 / SS)));                                                                         \
+    if (ddepth)                                                                                                                           \
+      hipLaunchKernelGGL(softmax_regress_bwd_kernel<SS>, grid, dim3(256), 0, (hipStream_t)stream, prob, hypos, hypos_per_pixel, ddepth,  \
+                         dprob, dlogit, B, D, h * w);                                                                                     \
+    else                                                                                                                                  \
+      hipLaunchKernelGGL(softmax_bwd_dprob_kernel<SS>, grid, dim3(256), 0, (hipStream_t)stream, prob, dprob, dlogit, B, D, h * w);        \
+  } while (0)
   if (S == 8) MDF_SRB(8); else if (S == 4) MDF_SRB(4); else if (S == 2) MDF_SRB(2); else MDF_SRB(1);
 #undef MDF_SRB
-  return mdf::check_launch("softmax_regress_bwd_kernel");
+  return mdf::check_launch(ddepth ? "softmax_regress_bwd_kernel" : "softmax_bwd_dprob_kernel");
 }
 
 static int prob_conv_dgrad_impl(const float* dlogit, const float* w, float* dx, int B, int D, int h, int wd, int C, const float* stat_y,
