@@ -205,6 +205,17 @@ int mdf_depth_regress_fwd(const float* prob, const float* hypos, int hypos_per_p
 int mdf_confidence_fwd(const float* prob, float* conf, int64_t* idx_out, int B, int D, int h, int w, void* stream);
 /* the same with the nearest x2 upsampling of net/core.py:76 folded in: conf2 [B,2h,2w]                            */
 int mdf_confidence_up2_fwd(const float* prob, float* conf2, int B, int D, int h, int w, void* stream);
+/* confidence_regress with the previous stage's confidence (net/unit/regress.py:9-25, all of it), any window of its signature:
+ *   cur  = sum prob[idx-pad_front .. idx-pad_front+n-1] (0 outside [0,D), ascending from 0.0f), idx as above; n in {1,2,4,8}
+ *   conf = w_last * bicubic_x2(last) + w_cur * cur;  last [B,H/2,W/2] (H, W even) or NULL: conf = cur, which at n=4,
+ *          pad_front=1 has the bits of mdf_confidence_fwd (up2: of mdf_confidence_up2_fwd).
+ *   bicubic_x2 = ATen upsample_bicubic2d, align_corners=False, scale 2, A=-0.75: taps k-2..k+1 with weights (-0.03515625,
+ *          0.26171875, 0.87890625, -0.10546875) at output 2k, taps k-1..k+2 with the reversed weights at 2k+1, tap indices
+ *          clamped; per tap row ((p0*c0 + p1*c1) + p2*c2) + p3*c3 along x, the same form along y, then the blend; every
+ *          product and sum rounded on its own.  Held to the reference's code in float64, not to ATen's fp32 bits.
+ *   up2 != 0: conf [B,2H,2W], every value at its 2x2 pixels (the nearest x2 of net/core.py:76); else conf [B,H,W].       */
+int mdf_confidence_cascade_fwd(const float* prob, const float* last, float w_last, float w_cur, int n, int pad_front, int up2,
+                               float* conf, int B, int D, int H, int W, void* stream);
 /* range mapping around the refinement net (net/unit/refine.py:29,44), per batch item b over n elements:
  *   mode 0: y = (x - lo[b]) / span[b]      mode 1: y = lo[b] + x * span[b]     (torch's separate roundings kept)   */
 int mdf_range_affine_fwd(const float* x, const float* lo, const float* span, int mode, float* y, int B, long long n, void* stream);

@@ -151,6 +151,7 @@ ngroups = (32, 16, 8)
 
 AGGREGATES = ("vector", "variance")
 CURVES = ("gauss0", "gauss1", "laplace")
+CONFIDENCES = ("last", "cascade")
 
 
 def parse_pair(text, kind):
@@ -176,16 +177,21 @@ def _curve_args(curves, thresh):
     return [None] + list(curves), [0.0] + [float(t) for t in thresh]
 
 
-def build_model(aggregate="vector", curves=None, prob_thresh=None):
+def build_model(aggregate="vector", curves=None, prob_thresh=None, confidence="last"):
     """A fresh CoreNet.  curves: the curve HyposByFit fits before stages 1 and 2, default ("gauss1", "laplace"); prob_thresh: their
     thresholds, default (0.95, 1e-5).  Every choice has the same state_dict (the slot has no parameters), so one checkpoint loads
     into all of them; which curves it was trained with is the caller's to keep.  aggregate="vector" (default): composed exactly like the reference's singleton.  aggregate="variance":
     the classic MVSNet variance cost volume in the Homoaggre slots (homo_aggregate_by_variance, homoaggregate.py:49-69), whose
     cost volume has the C = 2 G feature channels, so the regularisers' first layers are 64->16, 32->8, 16->8.  That model has no
     `Homoaggre.*` parameters and differently shaped `Regular.{0,1,2}.conv01` first layers: reference checkpoints (and those of
-    the vector model) do not load into it."""
+    the vector model) do not load into it.  confidence="last" (default): the confidence map comes from the last stage's probability
+    volume alone, as the reference's config composes it.  confidence="cascade": regress.confidence_cascade in the slot -- every stage
+    blends 0.8 * bicubic x2 of the previous stage's confidence with 0.2 of its own (regress.py:20-23), eval only; the slot has no
+    parameters, so the state_dict is the same."""
     if aggregate not in AGGREGATES:
         raise ValueError(f"aggregate={aggregate!r}: choose one of {AGGREGATES}")
+    if confidence not in CONFIDENCES:
+        raise ValueError(f"confidence={confidence!r}: choose one of {CONFIDENCES}")
     cv, th = _curve_args(curves, prob_thresh)
     hypos = nn.ModuleList([HyposByFit(ndepths[i], cv[i], th[i]) for i in range(stages - 1)])
     if aggregate == "variance":
@@ -197,7 +203,8 @@ def build_model(aggregate="vector", curves=None, prob_thresh=None):
         in_chs = ngroups
     regular = nn.ModuleList([RegularNet_3Scales(in_chs[0])] + [RegularNet_4Scales(c) for c in in_chs[1:]])
     return core.CoreNet(backbone.FPN_4Scales(chs), hypos, scale, aggre, regular,
-                        [regress.depth_regression, regress.confidence_regress], refine.RefineNet2())
+                        [regress.depth_regression, regress.confidence_cascade if confidence == "cascade" else regress.confidence_regress],
+                        refine.RefineNet2())
 
 
 model = build_model()

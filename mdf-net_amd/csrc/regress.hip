@@ -85,6 +85,86 @@ __global__ void confidence_up2_kernel(const float* __restrict__ prob, float* __r
   }
 }
 
+// ATen upsample_bicubic2d, align_corners=False, scale 2, A = -0.75: src = 0.5*(o+0.5)-0.5 = o/2 - 0.25, NOT clamped at 0, so the
+// fraction is 0.75 at every even o (taps k-2 .. k+1, o = 2k) and 0.25 at every odd o (taps k-1 .. k+2, o = 2k+1): one weight
+// quadruple, read forwards or backwards.  All four are exact in fp32.  Tap indices are clamped to [0, n_in-1].
+__device__ __forceinline__ void bicubic2_taps(int o, int n_in, int (&idx)[4], float (&c)[4]) {
+  constexpr float kW[4] = {-0.03515625f, 0.26171875f, 0.87890625f, -0.10546875f};
+  const int odd = o & 1, first = (o >> 1) - 2 + odd;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int t = first + j;
+    idx[j] = t < 0 ? 0 : (t > n_in - 1 ? n_in - 1 : t);
+    c[j] = odd ? kW[3 - j] : kW[j];
+  }
+}
+
+// confidence_regress(prob, last_confidence) of regress.py:9-25 with any window the reference's signature carries:
+//   cur  = sum prob[idx-pf .. idx-pf+nwin-1] (0 outside [0,D), ascending, from 0.0f), idx as in confidence_kernel;
+//   conf = w_last * bicubic_x2(last) + w_cur * cur       (last [B,h/2,w/2]; null: conf = cur, the bits of the kernels above
+//          at nwin = 4, pf = 1).
+// Fixed order, every product and sum rounded on its own (-ffp-contract=off, no fma): per tap row ((p0*c0 + p1*c1) + p2*c2) + p3*c3
+// along x, the same form along y over the four row results, then the blend.  up2: every value goes to its 2x2 pixels of
+// [B,2h,2w] (the nearest x2 of core.py:76), as in confidence_up2_kernel.  The 16 taps of `last` come through the caches: that
+// map is a quarter of this stage's size and neighbouring lanes share their taps.
+template <int DT>   // D at compile time (48 / 24 / 8: the model's stages; the plane loads leave together, see hypos_fit_kernel) or 0
+__global__ __launch_bounds__(kThreads) void confidence_cascade_kernel(const float* __restrict__ prob, const float* __restrict__ last,
+                                                                      float w_last, float w_cur, int nwin, int pf, int up2,
+                                                                      float* __restrict__ conf, int B, int D_rt, int h, int w) {
+  const int D = DT ? DT : D_rt;
+  const int hw = h * w;
+  const size_t n = (size_t)B * hw;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t b = i / hw, pix = i % hw;
+    const int y = (int)(pix / w), x = (int)(pix % w);
+    const float* p = prob + b * D * hw + pix;
+    mdf::CascadeSum ex;
+    float s = 0.0f;
+    if constexpr (DT != 0) {
+      float pv[DT];
+#pragma unroll
+      for (int d = 0; d < DT; ++d) pv[d] = p[(size_t)d * hw];
+#pragma unroll
+      for (int d = 0; d < DT; ++d) ex.add(pv[d] * (float)d);
+      long long idx = (long long)ex.result();
+      idx = idx < 0 ? 0 : (idx > D - 1 ? D - 1 : idx);
+      for (int k = (int)idx - pf; k < (int)idx - pf + nwin; ++k) {
+        float v = 0.0f;
+#pragma unroll
+        for (int d = 0; d < DT; ++d) v = (d == k) ? pv[d] : v;
+        s += v;
+      }
+    } else {
+      for (int d = 0; d < D; ++d) ex.add(p[(size_t)d * hw] * (float)d);
+      long long idx = (long long)ex.result();
+      idx = idx < 0 ? 0 : (idx > D - 1 ? D - 1 : idx);
+      for (int k = (int)idx - pf; k < (int)idx - pf + nwin; ++k) s += (k >= 0 && k < D) ? p[(size_t)k * hw] : 0.0f;
+    }
+    if (last) {
+      const int hl = h >> 1, wl = w >> 1;
+      const float* m = last + b * hl * wl;
+      int yi[4], xi[4];
+      float cy[4], cx[4], row[4];
+      bicubic2_taps(y, hl, yi, cy);
+      bicubic2_taps(x, wl, xi, cx);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float* mr = m + (size_t)yi[r] * wl;
+        row[r] = ((mr[xi[0]] * cx[0] + mr[xi[1]] * cx[1]) + mr[xi[2]] * cx[2]) + mr[xi[3]] * cx[3];
+      }
+      const float up = ((row[0] * cy[0] + row[1] * cy[1]) + row[2] * cy[2]) + row[3] * cy[3];
+      s = w_last * up + w_cur * s;
+    }
+    if (up2) {
+      float* o = conf + (b * 2 * h + 2 * y) * (size_t)(2 * w) + 2 * x;
+      *reinterpret_cast<float2*>(o) = make_float2(s, s);
+      *reinterpret_cast<float2*>(o + 2 * w) = make_float2(s, s);
+    } else {
+      conf[i] = s;
+    }
+  }
+}
+
 // Range mapping around the refinement net (refine.py:29,44), one launch each instead of two or three ATen ones; the separate
 // roundings of torch's op sequence are kept: mode 0: y = (x - lo[b]) / span[b];  mode 1: y = lo[b] + x * span[b]
 __global__ void range_affine_kernel(const float* __restrict__ x, const float* __restrict__ lo, const float* __restrict__ span, int mode,
@@ -394,6 +474,21 @@ extern "C" int mdf_confidence_up2_fwd(const float* prob, float* conf2, int B, in
   if (D == 8) hipLaunchKernelGGL(confidence_up2_kernel<8>, dim3(grid_for((size_t)B * h * w)), dim3(block_for((size_t)B * h * w)), 0, (hipStream_t)stream, prob, conf2, B, D, h, w);
   else hipLaunchKernelGGL(confidence_up2_kernel<0>, dim3(grid_for((size_t)B * h * w)), dim3(block_for((size_t)B * h * w)), 0, (hipStream_t)stream, prob, conf2, B, D, h, w);
   return mdf::check_launch("confidence_up2_kernel");
+}
+
+extern "C" int mdf_confidence_cascade_fwd(const float* prob, const float* last, float w_last, float w_cur, int n, int pad_front,
+                                          int up2, float* conf, int B, int D, int H, int W, void* stream) {
+  MDF_REQUIRE(prob && conf, "null pointer argument");
+  MDF_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, "bad shape");
+  MDF_REQUIRE(n == 1 || n == 2 || n == 4 || n == 8, "window length n must be 1, 2, 4 or 8 (n * avg_pool is a sum only then), got %d", n);
+  MDF_REQUIRE(pad_front >= 0, "pad_front must not be negative, got %d", pad_front);
+  MDF_REQUIRE(!last || (H % 2 == 0 && W % 2 == 0), "last confidence [B,H/2,W/2] needs even H and W, got %d x %d", H, W);
+  const size_t px = (size_t)B * H * W;
+#define MDF_CC(DT) hipLaunchKernelGGL(confidence_cascade_kernel<DT>, dim3(grid_for(px)), dim3(block_for(px)), 0, (hipStream_t)stream, prob, \
+                                      last, w_last, w_cur, n, pad_front, up2 ? 1 : 0, conf, B, D, H, W)
+  if (D == 48) MDF_CC(48); else if (D == 24) MDF_CC(24); else if (D == 8) MDF_CC(8); else MDF_CC(0);
+#undef MDF_CC
+  return mdf::check_launch("confidence_cascade_kernel");
 }
 
 extern "C" int mdf_range_affine_fwd(const float* x, const float* lo, const float* span, int mode, float* y, int B, long long n, void* stream) {

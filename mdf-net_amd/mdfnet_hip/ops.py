@@ -304,6 +304,21 @@ def confidence_up2(prob):
     return out
 
 
+def confidence_cascade(prob, last=None, n=4, pad_front=1, weights=(0.8, 0.2), up2=False):
+    """regress.py:9-25 with last_confidence: weights[0] * bicubic_x2(last) + weights[1] * sum prob[idx-pad_front .. +n-1], one launch.
+    prob [B,D,H,W]; last [B,H/2,W/2] or None (then the plain window sum); up2: the nearest x2 of core.py:76 folded in -> [B,2H,2W]."""
+    _need_gpu(prob, last)
+    b, d, h, w = prob.shape
+    if last is not None and tuple(last.shape) != (b, h // 2, w // 2):
+        raise ValueError(f"last confidence of shape {tuple(last.shape)}: expected {(b, h // 2, w // 2)} for a volume {tuple(prob.shape)}")
+    prob = _f32c(prob)
+    last_c = None if last is None else _f32c(last)      # (a local: a converted copy must outlive the launch's enqueue)
+    out = torch.empty((b, 2 * h, 2 * w) if up2 else (b, h, w), device=prob.device, dtype=torch.float32)
+    _abi("mdf_confidence_cascade_fwd", (prob.data_ptr(), None if last_c is None else last_c.data_ptr(), float(weights[0]), float(weights[1]),
+                                        int(n), int(pad_front), int(bool(up2)), out.data_ptr(), b, d, h, w, _stream(out),))
+    return out
+
+
 def range_affine(x, lo, span, mode):
     """mode 0: (x - lo[b]) / span[b]; mode 1: lo[b] + x * span[b]   (refine.py:29,44), x [B,...]."""
     _need_gpu(x, lo, span)

@@ -180,6 +180,11 @@ class CoreNet(torch.nn.Module):
         pyramids = self._pyramids(origin_imgs.float(), feature_cache, view_keys, pair_diff)
         depth = hypos = prob = None
         depths = []
+        # a Confidence_regress slot marked mdf_cascade (regress.confidence_cascade) is called after every stage with the previous
+        # stage's confidence (regress.py:20-23); eval only: training computes no confidence
+        cascade = not self.training and origin_imgs.is_cuda and getattr(self.Confidence_regress, "mdf_cascade", False)
+        conf = None
+        last_stage = len(self.Regular) - 1
         # Training on the HIP kernels: every stage's aggregation + regulariser is issued on a stream of its own.  The forward pass
         # gains nothing (stage s+1 needs stage s's depth: the streams are chained by events), but autograd runs a node's backward
         # on the stream of its forward, and the three stages' backward chains do not depend on each other -- the hypotheses are
@@ -223,6 +228,9 @@ class CoreNet(torch.nn.Module):
                 cuts.depth.append((depth, cut))
                 depth = cut
             depths.append(depth)
+            if cascade:
+                # (the last stage's call carries the nearest x2 of core.py:76: one launch, as on the default path)
+                conf = self.Confidence_regress(prob, last_confidence=conf, up2=stage == last_stage)
         depth = self.Refine(depth, depth_range)
         if cuts is not None and depth.requires_grad:
             cut = depth.detach().requires_grad_(True)       # the refinement net's backward (parameters only: refine.py:29 detaches
@@ -231,6 +239,8 @@ class CoreNet(torch.nn.Module):
         depths.append(depth)
         if self.training:
             return {"depth": depths}
+        if cascade:
+            return {"depth": depth, "confidence": conf}
         if getattr(self.Confidence_regress, "mdf_builtin", False) and prob.is_cuda:
             conf = ops.confidence_up2(prob.detach())          # regress.py:9-25 + the nearest x2 of core.py:76 in one launch
         else:
