@@ -619,6 +619,29 @@ int mdf_masked_smooth_l1_bwd_multi(const float* const* est, const float* const* 
                                    const void* floor_, int floor_f64, int floor_stride, int B, const float* dloss,
                                    const float* inv_count, float* const* dest, void* stream);
 
+/* ---- validation metrics of depth maps (no counterpart in the reference: it has no validation code).  Up to 8 maps
+ *      of different sizes in ONE reduction launch plus one small finalize launch.  Per map m (HOST arrays of nmaps entries):
+ *        est[m], gt[m]  [B][per_batch[m]] float;
+ *        hypos[m]       NULL, or the hypotheses a stage was given: [B][hypos_D[m]][per_batch[m]] when hypos_per_pixel[m], else
+ *                       [B][hypos_D[m]]; plane 0 is the interval's lower end `lo`, plane D-1 its upper end `hi`;
+ *        conf[m]        NULL, or [B][per_batch[m]] float.
+ *      Per batch item: depth_min at floor_[b*floor_stride] (float64 when floor_f64, else float32, as mdf_masked_smooth_l1_reduce
+ *      takes it) and thr[b][0..T-1] float absolute thresholds, 1 <= T <= 4.
+ *      A pixel is valid iff (double)gt > depth_min[b].  A valid pixel whose est (or conf, lo, hi where given) is not finite counts
+ *      in n_nonfinite and in nothing else.  e = fabsf(est - gt).  A table is [33][9] float64: row 0 over all pixels, rows 1..32 the
+ *      confidence bins min(max((int)floorf(conf * 32), 0), 31); columns n, n_nonfinite, sum_e, under[0..3] (e < thr, strict),
+ *      covered (lo <= gt && gt <= hi), sum_width (of the float hi - lo).  Bin rows fill n, sum_e, under[]; whatever has no input is 0.
+ *      No floating-point atomics: every block writes a partial table to `workspace` (mdf_depth_metrics_workspace bytes for the
+ *      same per_batch / nmaps / B; returns < 0 on a bad shape), mdf_depth_metrics_finalize adds them in block order into
+ *      tables [nmaps][33][9].  conf_mask: bit m set iff conf[m] was given to the reduction.  Run-to-run bit-identical.           */
+int64_t mdf_depth_metrics_workspace(const long long* per_batch, int nmaps, int B);
+int mdf_depth_metrics_reduce_multi(const float* const* est, const float* const* gt, const float* const* hypos, const int* hypos_D,
+                                   const int* hypos_per_pixel, const float* const* conf, const long long* per_batch, int nmaps,
+                                   const void* floor_, int floor_f64, int floor_stride, const float* thr, int T, int B,
+                                   void* workspace, long long workspace_bytes, void* stream);
+int mdf_depth_metrics_finalize(const void* workspace, long long workspace_bytes, const long long* per_batch, int nmaps, int B,
+                               int conf_mask, double* tables, void* stream);
+
 /* ---- feature-pyramid heads in training mode, the small algebra (net/unit/backbone.py:59-63: lat2, lat3, out2, out3, out4 -- 1x1 convs
  *      around two bilinear up-samplings, evaluated through the products O2 L2, O2 L3, O3 L3; train_ops.py:FPNHeadsComposedFn).
  *      Matrices are the Conv2d weights, row-major [out][in]: O2 [c2][cm], O3 [c3][cm], L2 [cm][c2], L3 [cm][c3], biases b2, b3 [cm].

@@ -110,6 +110,8 @@ class LoadDTU(DatasetsArgs):          # config.py:131-152
         self.train_label = _scan_ids("2 6-8 14 16 18-20 22 30-31 36 39 41-42 44-47 50-53 55 57-58 60-61 63-65 68-72 74 76 83-85 87-105 107-109 111-113 115-116 119-128")   # the 79 DTU training scans
         self.train_lighting_label = list(range(7))
         self.train_robust = True
+        self.val_label = _scan_ids("3 5 17 21 28 35 37 38 40 43 56 59 66 67 82 86 106 117")   # the 18 DTU validation scans (validate.py, train.py --val_every)
+        self.val_lighting_label = [3]
         self.eval_root = os.path.join(self.root_dir, "dtu1600x1200")
         self.eval_pair = os.path.join(self.eval_root, "pair.txt")
         self.eval_label = [int(s) for s in os.environ.get("MDF_DTU_SCANS", "11").split(",")]

@@ -13,10 +13,11 @@ from tools import data_io
 
 
 class LoadDataset(torch.utils.data.Dataset):
-    def __init__(self, datasetpath, nviews=5, robust_train=False):
+    def __init__(self, datasetpath, nviews=5, robust_train=False, listfile="training_list.txt"):
+        """listfile: the scan list under datasetpath -- "training_list.txt" (default) or "validation_list.txt" (validate.py)."""
         super().__init__()
         self.datasetpath, self.nviews, self.robust_train = datasetpath, nviews, robust_train
-        self.listfile = os.path.join(datasetpath, "training_list.txt")
+        self.listfile = os.path.join(datasetpath, listfile)
         self.all_compose = self._compose()
 
     def __len__(self):

@@ -70,6 +70,8 @@ KERNEL_FAMILY = {
     # loss.hip
     "masked_smooth_l1_reduce_kernel": CONTROL, "masked_smooth_l1_finalize_kernel": CONTROL, "masked_smooth_l1_bwd_kernel": CONTROL,
     "masked_smooth_l1_reduce_multi_kernel": CONTROL, "masked_smooth_l1_bwd_multi_kernel": CONTROL, "adam_step_kernel": CONTROL,
+    # depth_metrics.hip (validation metrics: one reduction over the maps, one fold of the block partials)
+    "depth_metrics_reduce_multi_kernel": CONTROL, "depth_metrics_finalize_kernel": CONTROL,
 }
 
 def function_name(rocprof_name):

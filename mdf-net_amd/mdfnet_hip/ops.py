@@ -330,6 +330,90 @@ def range_affine(x, lo, span, mode):
     return y
 
 
+METRIC_BINS = 32                     # confidence bins of a depth-metrics table (rows 1..32; row 0 is the whole map)
+METRIC_COLUMNS = ("n", "n_nonfinite", "sum_e", "under0", "under1", "under2", "under3", "covered", "sum_width")
+
+
+class MetricView:
+    """Named columns of a depth-metrics table [..., 1 + METRIC_BINS, 9] (views, no copies): n, n_nonfinite, sum_e, covered,
+    sum_width are [..., 33]; under is [..., 33, 4].  Row 0 is the whole map, rows 1..32 the confidence bins."""
+
+    def __init__(self, table):
+        self.table = table
+        for i, name in enumerate(METRIC_COLUMNS):
+            if not name.startswith("under"):
+                setattr(self, name, table[..., i])
+        self.under = table[..., 3:7]
+
+
+def depth_metrics(maps, floor, thresholds):
+    """Validation metrics of up to 8 depth maps of different sizes in one reduction launch and one finalize launch
+    (include/mdfnet_hip.h: mdf_depth_metrics_*).  maps: list of dicts with "est", "gt" [B,h,w] and optionally "hypos" ([B,D,h,w] or
+    [B,D,1,1]: the hypotheses a stage was given, whose first and last plane are the interval the cascade can recover) and "conf"
+    [B,h,w].  floor [B]: depth_min per item, float64 or float32 (any stride: depth_range[:, 0] is taken as it is).  thresholds
+    [B,T] (or [T], shared by the items), 1 <= T <= 4, absolute.  -> (table, view): table float64 [M, 33, 9] on the device, view
+    a MetricView of it.  Nothing synchronises; the workspace is a torch allocation.  Run-to-run bit-identical."""
+    if not 1 <= len(maps) <= 8:
+        raise ValueError(f"depth_metrics takes 1 to 8 maps, got {len(maps)}")
+    first = maps[0]["est"]
+    thr = thresholds if isinstance(thresholds, torch.Tensor) else torch.as_tensor(thresholds, dtype=torch.float32, device=first.device)
+    _need_gpu(floor, thr, *[t for m in maps for t in (m["est"], m["gt"], m.get("hypos"), m.get("conf"))])
+    b = first.shape[0]
+    thr = _f32c(thr)
+    if thr.dim() == 1:
+        thr = thr.reshape(1, -1).expand(b, -1).contiguous()
+    if thr.dim() != 2 or thr.shape[0] != b or not 1 <= thr.shape[1] <= 4:
+        raise ValueError(f"thresholds of shape {tuple(thr.shape)}: expected [{b}, 1..4]")
+    fl = floor.detach()
+    if fl.dtype not in (torch.float32, torch.float64):
+        fl = fl.float()
+    if fl.dim() == 0:
+        fl = fl.reshape(1)
+    if fl.dim() != 1 or fl.shape[0] not in (1, b):
+        raise ValueError(f"floor of shape {tuple(fl.shape)}: expected [{b}]")
+    fstride = fl.stride(0) if fl.shape[0] == b else 0
+    nm = len(maps)
+    keep, est, gt, hyp, hd, hpp, conf, per = [], [], [], [], [], [], [], []
+    conf_mask = 0
+    for i, m in enumerate(maps):
+        e, g = _f32c(m["est"].detach()), _f32c(m["gt"].detach())
+        if e.dim() != 3 or e.shape != g.shape or e.shape[0] != b:
+            raise ValueError(f"map {i}: est {tuple(e.shape)} and gt {tuple(g.shape)} must both be [{b}, h, w]")
+        h, w = e.shape[1:]
+        hy, cf = m.get("hypos"), m.get("conf")
+        if hy is not None:
+            if hy.dim() != 4 or hy.shape[0] != b:
+                raise ValueError(f"map {i}: hypos of shape {tuple(hy.shape)}: expected [{b}, D, h, w] or [{b}, D, 1, 1]")
+            hy, pp = _hypos_arg(hy.detach(), h, w)
+        if cf is not None:
+            cf = _f32c(cf.detach())
+            if cf.shape != e.shape:
+                raise ValueError(f"map {i}: conf of shape {tuple(cf.shape)}: expected {tuple(e.shape)}")
+            conf_mask |= 1 << i
+        keep.append((e, g, hy, cf))          # (converted copies must outlive the launch's enqueue)
+        est.append(e.data_ptr()); gt.append(g.data_ptr())
+        hyp.append(None if hy is None else hy.data_ptr()); hd.append(0 if hy is None else hy.shape[1]); hpp.append(0 if hy is None else pp)
+        conf.append(None if cf is None else cf.data_ptr())
+        per.append(h * w)
+    pb = (ctypes.c_int64 * nm)(*per)
+    nbytes = lib().mdf_depth_metrics_workspace(pb, nm, b)
+    if nbytes < 0:
+        check(int(nbytes), "mdf_depth_metrics_workspace")
+    dev = first.device
+    ws = torch.empty(nbytes // 8, device=dev, dtype=torch.float64)
+    table = torch.empty((nm, 1 + METRIC_BINS, len(METRIC_COLUMNS)), device=dev, dtype=torch.float64)
+    st = _stream(table)
+    arr = lambda vals: (ctypes.c_void_p * nm)(*vals)
+    nbytes_in = 4.0 * b * sum(p * (2 + (c is not None) + 2 * (hy is not None and pp_)) for p, c, hy, pp_ in zip(per, conf, hyp, hpp))
+    _abi("mdf_depth_metrics_reduce_multi", (arr(est), arr(gt), arr(hyp), (ctypes.c_int * nm)(*hd), (ctypes.c_int * nm)(*hpp), arr(conf), pb, nm,
+                                            fl.data_ptr(), int(fl.dtype == torch.float64), fstride, thr.data_ptr(), thr.shape[1], b,
+                                            ws.data_ptr(), nbytes, st), tag=f"depth metrics {nm} maps",
+         work={"bytes": nbytes_in + nbytes, "bound": "hbm"})
+    _abi("mdf_depth_metrics_finalize", (ws.data_ptr(), nbytes, pb, nm, b, conf_mask, table.data_ptr(), st))
+    del keep
+    return table, MetricView(table)
+
+
 _fit_row_cache = {}
 
 

@@ -51,6 +51,18 @@ def sum_over_ranks(value, device="cpu"):
     return float(t.item())
 
 
+def sum_tensor_over_ranks(t):
+    """The tensor form: one float64 all_reduce(SUM) of `t` over the ranks (on t's device: RCCL for a GPU tensor, gloo for a CPU one)
+    -> a new float64 tensor; `t` itself on a single process.  Integer-valued entries stay exact below 2^53; the last bits of
+    other sums depend on the world size (the order in which the ranks' shares are added)."""
+    t = t.to(torch.float64)
+    if not (dist.is_available() and dist.is_initialized()):
+        return t
+    t = t.clone()
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t
+
+
 def barrier():
     if dist.is_available() and dist.is_initialized():
         dist.barrier()

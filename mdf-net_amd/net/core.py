@@ -76,10 +76,13 @@ class CoreNet(torch.nn.Module):
         self.Depth_regress, self.Confidence_regress = Regress
         print("{} parameters: {}".format(self._get_name(), sum(p.data.nelement() for p in self.parameters())))
 
-    def forward(self, origin_imgs, extrinsics, intrinsics, depth_range, feature_cache=None, view_keys=None):
+    def forward(self, origin_imgs, extrinsics, intrinsics, depth_range, feature_cache=None, view_keys=None, stage_tap=None):
         """Same call as the reference (net/core.py:30).  Optional, for whole-scan evaluation: a dict
         `feature_cache` and per-view hashable `view_keys` [V] (batch 1) -- feature pyramids are then computed once per
-        image and reused while it serves as a source view of other items; results are identical."""
+        image and reused while it serves as a source view of other items; results are identical.
+        `stage_tap` (eval mode only; validation, mdfnet_hip/valmetrics.py): a list or a callable that is handed, after every stage,
+        {"stage": s, "hypos": the hypotheses the stage was given, "depth": its depth} and, after the refinement net,
+        {"stage": "final", "depth": ..., "confidence": ...} -- the tensors the forward holds anyway, nothing is computed for it."""
         if self.training and origin_imgs.is_cuda and layers.hip_train(self, origin_imgs):
             self._check_training_slots()
         with layers.model_mode(self.training):
@@ -90,7 +93,7 @@ class CoreNet(torch.nn.Module):
                 hostmirror.ensure((extrinsics, intrinsics, depth_range))
                 plan = controlplane.prepare(self, intrinsics, extrinsics, depth_range)
             with controlplane.active(plan):
-                return self._forward(origin_imgs, extrinsics, intrinsics, depth_range, feature_cache, view_keys)
+                return self._forward(origin_imgs, extrinsics, intrinsics, depth_range, feature_cache, view_keys, stage_tap)
 
     def _pair_diff_route(self, imgs):
         """True when this forward runs on pair-difference pyramids: eval on a GPU, the built-in FPN_4Scales with the (8,16,32,64)
@@ -161,7 +164,7 @@ class CoreNet(torch.nn.Module):
             return [tuple(lv.reshape(nb, nv, *lv.shape[1:])[:, v] for lv in f) for v in range(nv)]
         return [backbone(v) for v in torch.unbind(imgs, 1)]
 
-    def _forward(self, origin_imgs, extrinsics, intrinsics, depth_range, feature_cache=None, view_keys=None):
+    def _forward(self, origin_imgs, extrinsics, intrinsics, depth_range, feature_cache=None, view_keys=None, stage_tap=None):
         """imgs [B,V,3,H,W] (view 0 = reference), E [B,V,4,4], K [B,V,3,3], range [B,2]
         -> train: {"depth": [1/8, 1/4, 1/2, 1/1]};  eval: {"depth": [B,H,W], "confidence": [B,H,W]}."""
         if not self.training and not origin_imgs.is_cuda:
@@ -176,6 +179,11 @@ class CoreNet(torch.nn.Module):
             from mdfnet_hip import train_ops
             with torch.no_grad():
                 train_ops.prepack(self)
+        tap = None
+        if stage_tap is not None:
+            if self.training:
+                raise RuntimeError("CoreNet.forward(stage_tap=...) is an eval-mode hook (validation); call model.eval() first")
+            tap = stage_tap.append if isinstance(stage_tap, list) else stage_tap
         pair_diff = self._pair_diff_route(origin_imgs)
         pyramids = self._pyramids(origin_imgs.float(), feature_cache, view_keys, pair_diff)
         depth = hypos = prob = None
@@ -228,6 +236,8 @@ class CoreNet(torch.nn.Module):
                 cuts.depth.append((depth, cut))
                 depth = cut
             depths.append(depth)
+            if tap is not None:
+                tap({"stage": stage, "hypos": hypos, "depth": depth})
             if cascade:
                 # (the last stage's call carries the nearest x2 of core.py:76: one launch, as on the default path)
                 conf = self.Confidence_regress(prob, last_confidence=conf, up2=stage == last_stage)
@@ -240,10 +250,14 @@ class CoreNet(torch.nn.Module):
         if self.training:
             return {"depth": depths}
         if cascade:
+            if tap is not None:
+                tap({"stage": "final", "depth": depth, "confidence": conf})
             return {"depth": depth, "confidence": conf}
         if getattr(self.Confidence_regress, "mdf_builtin", False) and prob.is_cuda:
             conf = ops.confidence_up2(prob.detach())          # regress.py:9-25 + the nearest x2 of core.py:76 in one launch
         else:
             conf = self.Confidence_regress(prob)
             conf = torch.nn.functional.interpolate(conf.unsqueeze(1), scale_factor=2, mode="nearest").squeeze(1)
+        if tap is not None:
+            tap({"stage": "final", "depth": depth, "confidence": conf})
         return {"depth": depth, "confidence": conf}

@@ -66,7 +66,7 @@ def split_global_batch(batch_size, world):
     return batch_size // world
 
 
-def main():
+def build_parser():
     import config
     parser = argparse.ArgumentParser(description="train parameter setting")
     parser.add_argument("-p", "--pre_model", default=None, type=str)
@@ -77,7 +77,40 @@ def main():
     parser.add_argument("--curves", default="gauss1,laplace", type=str,
                         help="hypothesis curves fitted before stages 1 and 2: two of gauss0, gauss1, laplace")
     parser.add_argument("--prob_thresh", default="0.95,1e-5", type=str, help="their probability thresholds, each inside (0, 1)")
-    args = parser.parse_args()
+    parser.add_argument("--val_every", default=0, type=int,
+                        help="validate every N epochs on the dataset's validation items (validate.py; one line per validation in "
+                             "<pth>/epoch_val.txt); 0 (default): never")
+    return parser
+
+
+def make_val_dataset(args, nviews):
+    """The validation items for --val_every N > 0 (validate.val_dataset); None -- and nothing is read -- for 0."""
+    if args.val_every <= 0:
+        return None
+    from validate import val_dataset
+    return val_dataset(args.dataset, nviews)
+
+
+def validate_epoch(model, val_set, args, device, rank, world, epoch, pth_path, nworks=0):
+    """One eager validation pass over every rank's shard (between the replays of a recorded step too); rank 0 appends one JSON
+    line to <pth>/epoch_val.txt.  The model goes back to training mode."""
+    import json
+    from mdfnet_hip import valmetrics
+    from validate import parse_thresholds
+    thresholds, relative = parse_thresholds(None, args.dataset, False)
+    rep, _ = valmetrics.run_validation(model, val_set, device, thresholds, relative, rank, world, nworks)
+    model.train()
+    if rank == 0:
+        rep = dict(rep, epoch=epoch)
+        logging.info("epoch: " + str(epoch) + " validation:\n" + valmetrics.format_report(rep))
+        with open(os.path.join(pth_path, "epoch_val.txt"), "a") as f:
+            f.write(json.dumps(valmetrics.json_safe(rep)) + "\n")
+    return rep
+
+
+def main():
+    import config
+    args = build_parser().parse_args()
     rank, world, local = shard.init()
     if args.dataset == "dtu":
         load_args, train_args = config.LoadDTU(), config.TrainArgs()
@@ -90,6 +123,10 @@ def main():
         from load.blendedtrain import LoadDataset
         dataset = LoadDataset(datasetpath=load_args.train_root, nviews=train_args.nviews, robust_train=train_args.robust)
     device = train_args.DEVICE
+    if args.val_every > 0 and torch.device(device).type != "cuda":
+        raise SystemExit("train.py --val_every: validation runs the eval-mode forward on the hand-written MI355X kernels; it has no "
+                         "CPU rehearsal")
+    val_set = make_val_dataset(args, train_args.nviews)
     curves, thresh = config.parse_pair(args.curves, str), config.parse_pair(args.prob_thresh, float)
     default = args.aggregate == "vector" and curves == tuple(config.curve_calss[1:]) and thresh == tuple(config.prob_thresh[1:])
     model = config.model if default else config.build_model(aggregate=args.aggregate, curves=curves, prob_thresh=thresh)
@@ -125,6 +162,8 @@ def main():
         mean_loss = train_one_epoch(model, bucket, optimizer, criterion, batches, device, epoch=epoch)
         mean_loss = shard.sum_over_ranks(mean_loss, device if device.type == "cuda" else "cpu") / world
         bucket.broadcast_buffers(0)
+        if val_set is not None and epoch % args.val_every == 0:
+            validate_epoch(model, val_set, args, device, rank, world, epoch, train_args.pth_path, train_args.nworks)
         if rank == 0:
             logging.info("epoch: " + str(epoch) + " loss:" + str(mean_loss))
             with open(os.path.join(train_args.pth_path, "epoch_loss.txt"), "a") as f:
