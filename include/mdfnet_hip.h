@@ -413,6 +413,46 @@ int mdf_pts_knn(const void* index, long long n, long long index_bytes, const voi
 int mdf_pts_normals(const void* index, long long n, long long index_bytes, int k, const float* dirs, double* normals, double* cov,
                     void* stream);
 
+/* ---- Scene import from a sparse model: per-image depth ranges and the view-selection score, fp64 throughout -----------------------
+ * What turns "images + a COLMAP sparse model" into the cam files' depth range and pair.txt (tools/colmap); the reference has no
+ * counterpart.  No contraction, every operation rounded once, sums in the stated order, no floating-point atomics: the integer
+ * outputs, the ranges and the camera centres are a function of the inputs bit for bit, and the scores are reproducible run to run.
+ * Inputs (device unless marked HOST): rot [n_img][9], trans [n_img][3] fp64, world -> camera, row-major; pts [n_pts][3] fp64; the
+ * tracks as a CSR by point, track_off [n_pts + 1] int64 and track_img [n_obs] int32, image indices strictly ascending inside a
+ * track, so each (image, point) pair appears once.
+ *   camera centre      c_i[a] = -(((R_i[0][a] t_i[0]) + R_i[1][a] t_i[1]) + R_i[2][a] t_i[2]).
+ *   depth              z = (((r20 x) + r21 y) + r22 z) + t2 of an observation of image i.
+ *   mdf_view_depth_ranges   the n_i depths of image i in ascending order under the total order of their orderable bits (sign bit
+ *                      flipped for positive values, all bits for negative ones: -0.0 < +0.0; equal depths keep CSR order):
+ *                      range[i][0] = element min((long long)(q_lo * n_i), n_i - 1), range[i][1] the same with q_hi, the product in
+ *                      double; 0 <= q_lo <= q_hi <= 1.  count [n_img] int32 = n_i; an image with n_i = 0 gets NaN, NaN.
+ *   mdf_view_scores    for i < j and every point p both see, in ascending p: u = c_i - p, v = c_j - p, s = sqrt(((cx cx) + cy cy)
+ *                      + cz cz) of u x v (each component a b - c d), d = ((u0 v0) + u1 v1) + u2 v2, theta = atan2(s, d) *
+ *                      57.29577951308232 (degrees), e = theta - theta0, sigma = sigma1 if theta <= theta0 else sigma2,
+ *                      term = exp(-(e e) / ((2 sigma) sigma)).  score[i][j] = score[j][i] = 0 + the terms one after the other;
+ *                      shared[i][j] = shared[j][i] int32 = their number; both [n_img][n_img], zero elsewhere and on the diagonal.
+ *                      n_rec = the sum over tracks of t (t - 1) / 2, which the caller computes from track_off; more than
+ *                      2^31 - 4096 - 1 records (or observations) return MDF_EUNSUPPORTED.
+ *   status [4] int32 (device): status[0] = the OR of the MDF_VIEW_* bits below, 0 when every track was used.  A track with an
+ *                      offset outside [0, n_obs] or descending offsets, an image index outside [0, n_img) or indices that do not
+ *                      ascend strictly is skipped as a whole; a wrong n_rec sets MDF_VIEW_BAD_COUNT and nothing is written past
+ *                      n_rec.  The call still returns MDF_OK.
+ *   workspace          mdf_view_workspace(n_img, n_pts, n_obs, n_rec) bytes (0: sizes out of range), 16-byte aligned; n_rec = 0
+ *                      suffices for mdf_view_depth_ranges.  After mdf_view_scores it begins with the camera centres [n_img][3].
+ * n_img <= 32768.  Empty sizes (n_img <= 1, n_pts = 0, n_obs = 0, n_rec = 0) are valid and give zeros / NaN ranges.             */
+#define MDF_VIEW_BAD_IMAGE 1
+#define MDF_VIEW_NOT_ASCENDING 2
+#define MDF_VIEW_BAD_OFFSETS 4
+#define MDF_VIEW_BAD_COUNT 8
+long long mdf_view_workspace(int n_img, long long n_pts, long long n_obs, long long n_rec);
+int mdf_view_depth_ranges(const double* rot, const double* trans, int n_img, const double* pts, long long n_pts,
+                          const long long* track_off, const int* track_img, long long n_obs, double q_lo, double q_hi,
+                          void* workspace, long long ws_bytes, double* range, int* count, int* status, void* stream);
+int mdf_view_scores(const double* rot, const double* trans, int n_img, const double* pts, long long n_pts,
+                    const long long* track_off, const int* track_img, long long n_obs, long long n_rec, double theta0,
+                    double sigma1, double sigma2, void* workspace, long long ws_bytes, double* score, int* shared, int* status,
+                    void* stream);
+
 /* =====================================================================================================
  * Training path (BASELINE config 3; train.py:36-45 -> loss.backward()).  The reference has no explicit backward:
  * autograd differentiates the op chains cited above.  Each entry below is the hand-written forward-in-train-mode or

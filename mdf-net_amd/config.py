@@ -135,6 +135,21 @@ class LoadTanks(DatasetsArgs):        # config.py:169-180
         self.show_args()
 
 
+class LoadScene(DatasetsArgs):        # imported scenes (tools/colmap/main.py); no reference counterpart
+    def __init__(self, scene_root=None, scenes=()):
+        super().__init__()
+        self.eval_root = scene_root or os.path.join(self.root_dir, "scenes")
+        self.scenelist = list(scenes)
+        self.show_args()
+
+
+class EvalScene(EvalArgs):
+    def __init__(self, nviews=5):
+        super().__init__()
+        self.batch_size, self.nworks, self.nviews = 1, 1, nviews
+        self.show_args()
+
+
 # ----------------------------------------------------------------------------- net args (config.py:186-218)
 from net import core  # noqa: E402
 from net.unit import scale as _scale, backbone, regress, refine  # noqa: E402

@@ -100,7 +100,7 @@ def main():
     import config
     parser = argparse.ArgumentParser(description="eval parameter setting")
     parser.add_argument("-p", "--pre_model", default=None, type=str, help="Pre training model")
-    parser.add_argument("-d", "--dataset", default="dtu", type=str, choices=["dtu", "tanks"], help="Set dataset")
+    parser.add_argument("-d", "--dataset", default="dtu", type=str, choices=["dtu", "tanks", "scene"], help="Set dataset")
     parser.add_argument("-s", "--set", default="intermediate", type=str, choices=["intermediate", "advanced"])
     parser.add_argument("--aggregate", default="vector", type=str, choices=list(config.AGGREGATES),
                         help="cost-volume operator the checkpoint was trained with (train.py --aggregate)")
@@ -110,6 +110,9 @@ def main():
     parser.add_argument("--confidence", default="last", type=str, choices=list(config.CONFIDENCES),
                         help="last: confidence of the last stage's probability volume (the reference's composition); cascade: every stage "
                              "blends 0.8 x the bicubic x2 of the previous stage's confidence with 0.2 x its own (any checkpoint loads)")
+    parser.add_argument("--scene_root", default=None, type=str, help="-d scene: the folder tools/colmap/main.py wrote its scenes into")
+    parser.add_argument("--scenes", default="", type=str, help="-d scene: comma-separated scene folders under --scene_root")
+    parser.add_argument("--nviews", default=5, type=int, help="-d scene: views per item (the reference view and its best sources)")
     args = parser.parse_args()
     logging.info(args)
     rank, world, local = shard.init()
@@ -118,6 +121,13 @@ def main():
         from load.dtueval import LoadDataset
         dataset = LoadDataset(datasetpath=load_args.eval_root, pairpath=load_args.eval_pair,
                               scencelist=load_args.eval_label, nviews=eval_args.nviews)
+    elif args.dataset == "scene":
+        scenes = [s for s in args.scenes.split(",") if s]
+        if not scenes:
+            raise SystemExit("-d scene needs --scenes a,b (folders under --scene_root)")
+        load_args, eval_args = config.LoadScene(args.scene_root, scenes), config.EvalScene(args.nviews)
+        from load.sceneeval import LoadDataset
+        dataset = LoadDataset(datasetpath=load_args.eval_root, scenelist=load_args.scenelist, nviews=eval_args.nviews)
     else:
         load_args, eval_args = config.LoadTanks(tanks_set=args.set), config.EvalTanks()
         from load.tankseval import LoadDataset

@@ -14,6 +14,9 @@ _LAYOUT = {
     ("cam", "eval"): lambda s, v, l: (s, "cams", "%08d_cam.txt" % v),
     ("img", "tanks"): lambda s, v, l: (s, "images", "%08d.jpg" % v),
     ("cam", "tanks"): lambda s, v, l: (s, "cams_1", "%08d_cam.txt" % v),
+    # imported scenes (tools/colmap/main.py): per-scene images/ and cams/, any size that is a multiple of 32
+    ("img", "scene"): lambda s, v, l: (s, "images", "%08d.jpg" % v),
+    ("cam", "scene"): lambda s, v, l: (s, "cams", "%08d_cam.txt" % v),
     # BlendedMVS (768x576)
     ("img", "blendedmvs"): lambda s, v, l: (s, "blended_images", "%08d.jpg" % v),
     ("cam", "blendedmvs"): lambda s, v, l: (s, "cams", "%08d_cam.txt" % v),

@@ -85,6 +85,11 @@ SIGNATURES = {
     "mdf_pts_icp_sums": (c_int, [c_fp, c_i64, c_fp, c_i64, c_fp, c_fp, ctypes.c_double, c_fp, c_i64, c_fp, c_fp]),
     "mdf_pts_knn": (c_int, [c_fp, c_i64, c_i64, c_fp, c_fp, c_i64, c_i64, c_int, c_fp, c_fp, c_fp, c_fp]),
     "mdf_pts_normals": (c_int, [c_fp, c_i64, c_i64, c_int, c_fp, c_fp, c_fp, c_fp]),
+    "mdf_view_workspace": (c_i64, [c_int, c_i64, c_i64, c_i64]),
+    "mdf_view_depth_ranges": (c_int, [c_fp, c_fp, c_int, c_fp, c_i64, c_fp, c_fp, c_i64, ctypes.c_double, ctypes.c_double, c_fp, c_i64,
+                                      c_fp, c_fp, c_fp, c_fp]),
+    "mdf_view_scores": (c_int, [c_fp, c_fp, c_int, c_fp, c_i64, c_fp, c_fp, c_i64, c_i64] + [ctypes.c_double] * 3 + [c_fp, c_i64, c_fp,
+                                c_fp, c_fp, c_fp]),
     "mdf_bn_stats_fwd": (c_int, [c_fp, c_i64, c_int, c_int, c_fp, c_fp]),
     "mdf_bn_finalize_fwd": (c_int, [c_fp, c_fp, c_fp, ctypes.c_float, ctypes.c_float, c_i64, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_fp]),
     "mdf_bn_relu_apply_fwd": (c_int, [c_fp, c_fp, c_fp, c_fp, c_i64, c_int, c_int, c_fp]),

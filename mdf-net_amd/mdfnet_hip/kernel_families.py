@@ -67,6 +67,10 @@ KERNEL_FAMILY = {
     "pts_icp_moment_kernel": POINT_EVAL, "pts_icp_final_kernel": POINT_EVAL,
     # point_knn.hip (point-cloud post-processing: k nearest neighbours, normal estimation)
     "pts_knn_kernel": POINT_EVAL, "pts_normals_kernel": POINT_EVAL,
+    # view_select.hip (scene import: depth ranges and view-selection scores from a sparse model; sorts through point_index.hip)
+    "view_centre_kernel": POINT_EVAL, "view_track_kernel": POINT_EVAL, "view_fill_kernel": POINT_EVAL, "view_depth_key_kernel": POINT_EVAL,
+    "view_regroup_kernel": POINT_EVAL, "view_range_kernel": POINT_EVAL, "view_expand_kernel": POINT_EVAL, "view_term_kernel": POINT_EVAL,
+    "view_sum_kernel": POINT_EVAL,
     # loss.hip
     "masked_smooth_l1_reduce_kernel": CONTROL, "masked_smooth_l1_finalize_kernel": CONTROL, "masked_smooth_l1_bwd_kernel": CONTROL,
     "masked_smooth_l1_reduce_multi_kernel": CONTROL, "masked_smooth_l1_bwd_multi_kernel": CONTROL, "adam_step_kernel": CONTROL,

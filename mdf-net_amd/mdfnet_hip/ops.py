@@ -1404,6 +1404,89 @@ def voxel_downsample(pts, voxel, attrs=None, return_counts=False):
     return res[0] if len(res) == 1 else res
 
 
+VIEW_STATUS = {1: "an image index outside [0, n_img)", 2: "a track whose image indices do not ascend strictly",
+               4: "track offsets outside [0, n_obs] or descending", 8: "a record count that does not match the tracks"}
+
+
+def _view_inputs(rot, trans, pts, track_off, track_img):
+    """The scene of the view-selection entries as contiguous GPU tensors -> (rot [N,9], trans [N,3], pts [P,3], track_off [P+1] int64,
+    track_img [T] int32, n_rec = the sum over tracks of t(t-1)/2, computed from the offsets)."""
+    _need_gpu(rot, trans, pts, track_off, track_img)
+    rot = rot.to(torch.float64).reshape(-1, 9).contiguous()
+    trans = trans.to(torch.float64).reshape(-1, 3).contiguous()
+    pts = _pts64(pts)
+    track_off = track_off.to(torch.int64).reshape(-1).contiguous()
+    track_img = track_img.to(torch.int32).reshape(-1).contiguous()
+    if trans.shape[0] != rot.shape[0]:
+        raise ValueError(f"{rot.shape[0]} rotations, {trans.shape[0]} translations")
+    if track_off.numel() != pts.shape[0] + 1:
+        raise ValueError(f"track_off has {track_off.numel()} entries for {pts.shape[0]} points ({pts.shape[0] + 1} expected)")
+    t = (track_off[1:] - track_off[:-1]).clamp(min=0, max=1 << 20)       # (a bad offset is the kernel's to report)
+    n_rec = int((t * (t - 1) // 2).sum().item())
+    return rot, trans, pts, track_off, track_img, n_rec
+
+
+def _view_workspace(n, p, t, n_rec, dev, what):
+    nbytes = int(lib().mdf_view_workspace(n, p, t, n_rec))
+    if nbytes <= 0:
+        raise ValueError(f"{what}: {n} images, {p} points, {t} observations and {n_rec} pair records are too many")
+    return torch.empty(nbytes, device=dev, dtype=torch.uint8)
+
+
+def _view_status(status, what):
+    bits = int(status[0].item())
+    if bits:
+        raise ValueError(f"{what}: the tracks hold " + "; ".join(m for b, m in VIEW_STATUS.items() if bits & b))
+
+
+def view_depth_ranges(rot, trans, pts, track_off, track_img, quantiles=(0.01, 0.99)):
+    """Per-image depth range from a sparse model (mdf_view_depth_ranges): the depths z = r2 . p + t2 of every image's observations
+    in ascending order, range[i] = the elements min(int(q * n_i), n_i - 1) for the two quantiles.  rot [N,3,3], trans [N,3]
+    world -> camera, pts [P,3]; tracks as a CSR by point (track_off [P+1], track_img [T], strictly ascending inside a track).
+    -> range [N,2] fp64 (NaN for an image without observations), count [N] int32, on the GPU."""
+    rot, trans, pts, track_off, track_img, _ = _view_inputs(rot, trans, pts, track_off, track_img)
+    n, p, t, dev = rot.shape[0], pts.shape[0], track_img.numel(), pts.device
+    q_lo, q_hi = float(quantiles[0]), float(quantiles[1])
+    if not (0.0 <= q_lo <= q_hi <= 1.0):
+        raise ValueError(f"quantiles {quantiles} must satisfy 0 <= q_lo <= q_hi <= 1")
+    ws = _view_workspace(n, p, t, 0, dev, "view_depth_ranges")
+    rng = torch.empty((max(n, 1), 2), device=dev, dtype=torch.float64)
+    cnt = torch.empty(max(n, 1), device=dev, dtype=torch.int32)
+    status = torch.zeros(4, device=dev, dtype=torch.int32)
+    _abi("mdf_view_depth_ranges", (rot.data_ptr() if n else None, trans.data_ptr() if n else None, n, pts.data_ptr() if p else None, p,
+                                   track_off.data_ptr(), track_img.data_ptr() if t else None, t, ctypes.c_double(q_lo),
+                                   ctypes.c_double(q_hi), ws.data_ptr(), ws.numel(), rng.data_ptr(), cnt.data_ptr(), status.data_ptr(),
+                                   _stream(pts)), tag=f"n{n} t{t}", work={"points": float(t), "bound": "hbm"})
+    _view_status(status, "view_depth_ranges")
+    return rng[:n], cnt[:n]
+
+
+def view_scores(rot, trans, pts, track_off, track_img, theta0=5.0, sigma1=1.0, sigma2=10.0, return_centres=False):
+    """View-selection score of every image pair (mdf_view_scores): over the points both images see, in ascending point index, the sum
+    of exp(-(theta - theta0)^2 / (2 sigma^2)) with theta the triangulation angle in degrees (atan2 of the cross and dot products of
+    the rays to the two camera centres) and sigma = sigma1 up to theta0, sigma2 beyond.  Inputs as for view_depth_ranges.
+    -> score [N,N] fp64 (symmetric, zero diagonal), shared [N,N] int32 (points in common) (, centres [N,3] fp64), on the GPU."""
+    rot, trans, pts, track_off, track_img, n_rec = _view_inputs(rot, trans, pts, track_off, track_img)
+    n, p, t, dev = rot.shape[0], pts.shape[0], track_img.numel(), pts.device
+    theta0, sigma1, sigma2 = float(theta0), float(sigma1), float(sigma2)
+    if not (sigma1 > 0 and sigma2 > 0 and sigma1 < float("inf") and sigma2 < float("inf") and abs(theta0) < float("inf")):
+        raise ValueError(f"theta0={theta0}, sigma1={sigma1}, sigma2={sigma2}: theta0 finite and both sigmas finite and > 0 are needed")
+    ws = _view_workspace(n, p, t, n_rec, dev, "view_scores")
+    score = torch.empty((max(n, 1), max(n, 1)), device=dev, dtype=torch.float64)
+    shared = torch.empty((max(n, 1), max(n, 1)), device=dev, dtype=torch.int32)
+    status = torch.zeros(4, device=dev, dtype=torch.int32)
+    _abi("mdf_view_scores", (rot.data_ptr() if n else None, trans.data_ptr() if n else None, n, pts.data_ptr() if p else None, p,
+                             track_off.data_ptr(), track_img.data_ptr() if t else None, t, n_rec, ctypes.c_double(theta0),
+                             ctypes.c_double(sigma1), ctypes.c_double(sigma2), ws.data_ptr(), ws.numel(), score.data_ptr(),
+                             shared.data_ptr(), status.data_ptr(), _stream(pts)), tag=f"n{n} r{n_rec}",
+         work={"points": float(n_rec), "bound": "hbm"})
+    _view_status(status, "view_scores")
+    res = (score[:n, :n], shared[:n, :n])
+    if return_centres:
+        res += (ws[:n * 24].clone().view(torch.float64).reshape(n, 3),)
+    return res
+
+
 def icp_sums(src, tgt, nearest, d2, threshold):
     """The sums of one point-to-point ICP step (mdf_pts_icp_sums) over the pairs (src[i], tgt[nearest[i]]) with nearest[i] >= 0 and
     sqrt(d2[i]) < threshold -> host numpy [17]: inlier count, sum of d^2, source centroid, target centroid, H (3x3 row-major,

@@ -1,6 +1,6 @@
 """Depth-map filtering + fusion driver (counterpart of the reference's tools/filter/dynamic_filter_gpu.py:12-301).
 
-Same entry points (`filter`, `check_geometric_consistency`), CLI flags (-f/-d/-s/-e/-r/-o) and outputs
+Same entry points (`filter`, `check_geometric_consistency`), CLI flags (-f/-d/-s/-e/-r/-o; -d scene --scans a,b for scenes tools/colmap/main.py imported) and outputs
 (<eval>/<scan>/<filter>/{%08d_photo,_geo,_final}.png, <ref>_depth_est.pfm, <scan>.ply), but every reference view is ONE
 fused HIP kernel over all its source views (mdf_consistency_fuse_fwd) instead of ~40 tensor passes per source view, and
 scans shard over ranks (one process per GPU, no collective).  The .ply is written directly (binary little-endian, the
@@ -95,11 +95,12 @@ def filter(dataset_root, scan, img_folder, cam_folder, eval_folder, filter_folde
 def main():
     parser = argparse.ArgumentParser(description="filter to mask cloudpoints...")
     parser.add_argument("-f", "--filter_folder", default="filter", type=str)
-    parser.add_argument("-d", "--dataset", default="tanks", type=str, help="dtu or tanks")
+    parser.add_argument("-d", "--dataset", default="tanks", type=str, help="dtu, tanks or scene")
     parser.add_argument("-s", "--set", default="intermediate", type=str)
     parser.add_argument("-e", "--eval_folder", default=os.environ.get("MDF_OUTPUT_ROOT", "/hy-tmp/outputs"), type=str)
     parser.add_argument("-r", "--root_folder", default=os.environ.get("MDF_DATA_ROOT", "/hy-nas"), type=str)
     parser.add_argument("-o", "--outply_folder", default=None, type=str)
+    parser.add_argument("--scans", default="", type=str, help="-d scene: comma-separated scene folders under -r (tools/colmap/main.py)")
     args = parser.parse_args()
     rank, world, _ = shard.init()
     if args.dataset == "dtu":
@@ -111,8 +112,13 @@ def main():
         scans = {"intermediate": ["Family", "Francis", "Horse", "Lighthouse", "M60", "Panther", "Playground", "Train"],
                  "advanced": ["Auditorium", "Ballroom", "Courtroom", "Museum", "Palace", "Temple"]}[args.set]
         img_folder, cam_folder, ncond = "images", "cams_1", (5 if args.set == "intermediate" else 1)
+    elif args.dataset == "scene":
+        root, scans = args.root_folder, [s for s in args.scans.split(",") if s]
+        if not scans:
+            raise SystemExit("-d scene needs --scans a,b (folders under -r)")
+        img_folder, cam_folder, ncond = "images", "cams", 3
     else:
-        raise SystemExit("please use dtu or tanks dataset")
+        raise SystemExit("please use dtu, tanks or scene dataset")
     for i in shard.shard_items(len(scans), rank, world):     # scans are independent: shard them, no collective
         t0 = time.time()
         filter(root, scans[i], img_folder, cam_folder, args.eval_folder, args.filter_folder, args.outply_folder, 0.8, ncond, 4, 1300)
