@@ -43,6 +43,32 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nblk) {
   const unsigned base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
   return base + (bid >> 3);
 }
+// The same share, for persistent kernels whose waves walk it themselves: the first item and the length of the contiguous chunk of
+// n items that block bid's XCD (bid & 7) owns (the first n % 8 XCDs hold one more).  xcd_remap(bid, n) = xcd_chunk(bid, n).start +
+// (bid >> 3); it keeps its own lines because the kernels that call it compile to the same instructions only that way.
+struct XcdChunk { unsigned start, len; };
+__device__ __forceinline__ XcdChunk xcd_chunk(unsigned bid, unsigned n) {
+  const unsigned x = bid & 7u, q = n >> 3, r = n & 7u;
+  return XcdChunk{(x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q, q + (x < r ? 1u : 0u)};
+}
+
+// Kernels that need more than the default 64 KB of dynamic LDS: hipFuncAttributeMaxDynamicSharedMemorySize, set before the first
+// launch.  The attribute is a per-DEVICE property of the function (several GPUs in one process, DataParallel-style), so there is one
+// flag per device and -- KERN being a template argument -- per kernel instantiation; a device id outside the table sets it on every
+// call.  Benign race: the call is idempotent.
+template <auto KERN>
+inline int ensure_dynamic_lds(size_t bytes) {
+  static bool done_dev[64] = {};
+  int dev_id = 0;
+  (void)hipGetDevice(&dev_id);
+  bool& done = done_dev[(dev_id >= 0 && dev_id < 64) ? dev_id : 0];
+  if (!done || dev_id >= 64) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return fail(MDF_EHIP, "hipFuncSetAttribute(dynamic LDS %zu): %s", bytes, hipGetErrorString(e));
+    done = true;
+  }
+  return MDF_OK;
+}
 
 // ATen's CPU float sum (SumKernel.cpp multi_row_sum / cascade_sum): elements are added sequentially into
 // level 0; after every 16 elements level 0 is folded into level 1 (after every 256 into level 2, ...); the
@@ -70,7 +96,7 @@ struct CascadeSum {
   __device__ __forceinline__ float result() const { return ((l0 + l1) + l2) + l3; }
 };
 
-// Epilogue sums of the training path (conv3d.hip / conv_lds.hip; all null / 0 for inference): see ConvParams::stat_mode.
+// Epilogue sums of the training path (conv3d.hip / conv_lds.hip; all null / 0 for inference): see ConvParams::stat_mode (conv3d_common.h).
 struct ConvStat {
   int mode;
   const float* y;
@@ -107,3 +133,15 @@ __device__ __forceinline__ void conv_stat_send(const double* tab, double* out, l
   do {                         \
     if (!(cond)) return mdf::fail(MDF_EARG, __VA_ARGS__); \
   } while (0)
+
+namespace mdf {
+// the epilogue-sum arguments of the training entries (mdf_conv2d_train_fwd, mdf_conv3d_train_fwd)
+inline int check_stat(int stat_mode, const float* stat_y, const float* stat_aux, const double* stat_out, int nslices, int Cout) {
+  MDF_REQUIRE(stat_mode == 1 || stat_mode == 2, "stat_mode=%d not in {1 (sum y, sum y^2), 2 (BatchNorm-backward sums)}", stat_mode);
+  MDF_REQUIRE(stat_out, "stat_out is null");
+  MDF_REQUIRE(nslices >= 1 && nslices <= 64, "nslices=%d out of range [1,64]", nslices);
+  MDF_REQUIRE(stat_mode == 1 || (stat_y && stat_aux), "stat_mode 2 needs stat_y and stat_aux");
+  MDF_REQUIRE(Cout % 4 == 0 && Cout >= 8 && Cout <= 64, "epilogue sums are built for Cout in {8,..,64}, Cout %% 4 == 0 (got %d)", Cout);
+  return MDF_OK;
+}
+}  // namespace mdf

@@ -11,7 +11,7 @@
 //
 // LDS image of one plane:  [cin / KPL][S] vectors of KPL floats, S = plane-tile voxels rounded up to the residue (round_s)
 // that puts the lane groups of ds_read_b128 (and the two halves of ds_read_b64) on disjoint banks for every tap shift.
-// GEMM orientation and weight packing are those of conv3d.hip:  D[cout][voxel] = W[cout][k] * X[k][voxel].
+// GEMM orientation is that of conv3d.hip, weight packing conv_pack.hip's:  D[cout][voxel] = W[cout][k] * X[k][voxel].
 #include <cstdlib>
 #include <mutex>
 #include <type_traits>
@@ -109,7 +109,8 @@ __device__ __forceinline__ void step(const float* const (&planes)[KD], __amdgpu_
           o[2] = rr.z + o[2] * p.res_scale; o[3] = rr.w + o[3] * p.res_scale;
         }
         *reinterpret_cast<float4*>(p.y + oi) = make_float4(o[0], o[1], o[2], o[3]);
-        if constexpr (ST != 0) stat_accum<C, ST>(p, lds_base_, oi, c0, o, ps, pq);
+        // (ST is the mode: the two modes are separate instantiations -- together they cost the 2-D kernels an occupancy step)
+        if constexpr (ST != 0) stat_accum<ST, C::SAUX_OFF>(ST, p.stat_y, lds_base_, oi, c0, o, ps, pq);
       } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -117,7 +118,7 @@ __device__ __forceinline__ void step(const float* const (&planes)[KD], __amdgpu_
         }
       }
     }
-    if constexpr (ST != 0) stat_commit<C>(lds_base_, c0, n16, ps, pq);
+    if constexpr (ST != 0) stat_commit<C::STAT_OFF>(lds_base_, c0, n16, ps, pq);
   }
 }
 
@@ -130,7 +131,7 @@ __device__ __forceinline__ void static_for(F&& f) {
 }
 
 // ---- Winograd form (Cfg::WINO) ---------------------------------------------------------------------------------
-// Weight fragments (pack_weights_wino_kernel, conv3d.hip): [kd][chunk][ab = a*4+b][nt][lane][4], U = G g_kd G^T.
+// Weight fragments (conv_pack.hip: pack_wino_elem): [kd][chunk][ab = a*4+b][nt][lane][4], U = G g_kd G^T.
 #ifndef MDF_WG_AHEAD
 #define MDF_WG_AHEAD 2
 #endif
@@ -309,14 +310,14 @@ __device__ __forceinline__ void wino_epilogue(const f32x4 (&acc)[16][C::NTP], in
           o[2] = rr.z + o[2] * p.res_scale; o[3] = rr.w + o[3] * p.res_scale;
         }
         *reinterpret_cast<float4*>(p.y + oi) = make_float4(o[0], o[1], o[2], o[3]);
-        if constexpr (ST != 0) stat_accum<C, ST>(p, lds_base_, oi, c0, o, ps, pq);
+        if constexpr (ST != 0) stat_accum<ST, C::SAUX_OFF>(ST, p.stat_y, lds_base_, oi, c0, o, ps, pq);      // (ST is the mode, as in step)
       }
     }
-    if constexpr (ST != 0) stat_commit<C>(lds_base_, c0, n16, ps, pq);
+    if constexpr (ST != 0) stat_commit<C::STAT_OFF>(lds_base_, c0, n16, ps, pq);
   }
 }
 
-// Weight fragments (pack_weights_wino_kernel, conv3d.hip): [kd][chunk][ab = a*4+b][nt][lane][4], U = G g_kd G^T.
+// Weight fragments (conv_pack.hip: pack_wino_elem): [kd][chunk][ab = a*4+b][nt][lane][4], U = G g_kd G^T.
 template <typename C, int COUT, int NKD, int ST = 0>
 __device__ __forceinline__ void step_wino(const float* const (&planes)[NKD], __amdgpu_buffer_rsrc_t wres, int wvoff, const LdsConvParams& p,
                                           int b, int d, int d_lim, int h, int w0, int q, int n16, const float (&wfirst)[2][C::NT][C::KPL]) {
@@ -825,18 +826,7 @@ int launch_lds(LdsConvParams& p, hipStream_t st) {
     p.n_items = (int)g;                          // = grid size (static partition)
     p.dch = 1; p.dchunks = 1;
   }
-  // the dynamic-LDS attribute is a per-DEVICE property of the function: one flag per device (several GPUs in one
-  // process, DataParallel-style).  Benign race: the call is idempotent.
-  static bool attr_done_dev[64] = {};     // (one per template instantiation, ST included)
-  int dev_id = 0;
-  (void)hipGetDevice(&dev_id);
-  bool& attr_done = attr_done_dev[(dev_id >= 0 && dev_id < 64) ? dev_id : 0];
-  if (!attr_done || dev_id >= 64) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_lds_kernel<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, ST>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds);
-    if (e != hipSuccess) return mdf::fail(MDF_EHIP, "hipFuncSetAttribute(dynamic LDS %zu): %s", kLds, hipGetErrorString(e));
-    attr_done = true;
-  }
+  if (int rc = mdf::ensure_dynamic_lds<&conv_lds_kernel<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, ST>>(kLds)) return rc;   // (one flag per instantiation, ST included)
   int grid = max_grid;
   grid = mdf::env_pos("MDF_CONV_GRID", grid);   // dev: residency experiments
   if (grid > p.n_items) grid = p.n_items;
@@ -1041,4 +1031,50 @@ int mdf_conv_lds_dispatch(const float* x, const float* wpack, const float* alpha
   LDS_CASE(16, 16, 32, 1, 3, 1, 2) LDS_CASE(32, 32, 64, 1, 3, 1, 1)   // input gradients of the k5-s2 layers (training): 3x3 over dy, 4 parity classes as channels
   LDS_CASE(16, 16, 4, 1, 3, 1, 4) LDS_CASE(8, 8, 4, 1, 3, 1, 4)   // prob head as per-plane partial sums (prob_head.hip)
   return MDF_EUNSUPPORTED;
+}
+
+// ---- the 2-D entry points -------------------------------------------------------------------------------------------------------
+using mdf::ConvStat, mdf::padded_cin;
+
+int mdf_conv1x1_dispatch(const float* x, const float* wpack, const float* alpha, const float* beta, const float* res, float res_scale,
+                         const float* res_up, float* y, int B, int H, int W, int Cin, int Cout, int relu, void* stream);      // conv1x1.hip
+
+static int conv2d_entry(const float* x, const float* wpack, const float* alpha, const float* beta, const float* res,
+                        float res_scale, const float* res_up, float* y, int B, int H, int W, int Cin_mem, int Cout, int ksize, int stride,
+                        int relu, int planar_in, int pixel_shuffle2, void* stream, const ConvStat* stat) {
+  MDF_REQUIRE(x && wpack && y, "null pointer argument");
+  MDF_REQUIRE(B > 0 && H > 0 && W > 0, "bad shape");
+  MDF_REQUIRE((long long)B * H * W * Cin_mem < (1ll << 31), "input too large for 32-bit offsets");
+  MDF_REQUIRE(res_up == nullptr || (stride == 1 && H % 2 == 0 && W % 2 == 0 && Cout % 4 == 0),
+              "res_up needs stride 1, even H and W, Cout %% 4 == 0");
+  MDF_REQUIRE(!planar_in || Cin_mem < 4, "planar (NCHW) input is supported for Cin < 4 only (the image layer)");
+  MDF_REQUIRE(!pixel_shuffle2 || ((Cout == 32 || (Cout == 64 && Cin_mem == 32 && ksize == 3)) && stride == 1 && !res && !res_up && !stat), "pixel_shuffle2 output is built for Cout = 32 (and 32 -> 64 k3), stride 1, no residual, no epilogue sums");
+  if (ksize == 1 && stride == 1 && !stat && !planar_in && !pixel_shuffle2) {   // 1x1 layers: streaming kernel (conv1x1.hip)
+    const int rc1 = mdf_conv1x1_dispatch(x, wpack, alpha, beta, res, res_scale, res_up, y, B, H, W, Cin_mem, Cout, relu, stream);
+    if (rc1 != MDF_EUNSUPPORTED) return rc1;
+  }
+  const int rc = mdf_conv_lds_dispatch(x, wpack, alpha, beta, res, res_scale, res_up, y, B, 1, H, W, padded_cin(Cin_mem), Cin_mem, Cout, 1,
+                                       ksize, stride, relu, stream, planar_in, pixel_shuffle2, stat);
+  if (rc == MDF_EUNSUPPORTED)
+    return mdf::fail(MDF_EUNSUPPORTED, "conv2d Cin=%d Cout=%d k=%d stride=%d%s is not built", Cin_mem, Cout, ksize, stride, stat ? " (with epilogue sums)" : "");
+  return rc;
+}
+
+extern "C" int mdf_conv2d_fwd(const float* x, const float* wpack, const float* alpha, const float* beta, const float* res,
+                              float res_scale, const float* res_up, float* y, int B, int H, int W, int Cin_mem, int Cout, int ksize, int stride,
+                              int relu, int planar_in, int pixel_shuffle2, void* stream) {
+  return conv2d_entry(x, wpack, alpha, beta, res, res_scale, res_up, y, B, H, W, Cin_mem, Cout, ksize, stride, relu, planar_in, pixel_shuffle2,
+                      stream, nullptr);
+}
+
+// Training: the RAW 2-D conv (no scale / shift / ReLU) whose epilogue also accumulates per-channel sums of its output, per
+// BatchNorm group (ngroups consecutive sets of B/ngroups images): see ConvParams::stat_mode.  stat_out [nslices][ngroups][2*Cout]
+// fp64, zero-initialised by the caller (the sums are the totals over the slices); stat_aux [ngroups][4*Cout].
+extern "C" int mdf_conv2d_train_fwd(const float* x, const float* wpack, float* y, int B, int H, int W, int Cin_mem, int Cout, int ksize,
+                                    int stride, int planar_in, int stat_mode, const float* stat_y, const float* stat_aux, double* stat_out,
+                                    int nslices, int ngroups, void* stream) {
+  if (int rc = mdf::check_stat(stat_mode, stat_y, stat_aux, stat_out, nslices, Cout)) return rc;
+  MDF_REQUIRE(ngroups >= 1 && B % ngroups == 0, "B=%d is not a multiple of ngroups=%d", B, ngroups);
+  const ConvStat st{stat_mode, stat_y, stat_aux, stat_out, B / ngroups, nslices};
+  return conv2d_entry(x, wpack, nullptr, nullptr, nullptr, 1.0f, nullptr, y, B, H, W, Cin_mem, Cout, ksize, stride, 0, planar_in, 0, stream, &st);
 }

@@ -5,15 +5,13 @@
 #include <cstdlib>
 #include <type_traits>
 #include "common.h"
+#include "conv3d_common.h"      // f32x4, lds_add_f64 / row16_sum, the ST epilogue pair stat_accum / stat_commit
 
 namespace {
 
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 struct LdsConvParams {
   const float* x;      // [B,D,H,W,CIN_MEM]
-  const float* wpack;  // conv3d.hip packing (taps = KD*KHW*KHW)
+  const float* wpack;  // conv_pack.hip packing (taps = KD*KHW*KHW)
   const float* alpha;  // [COUT] or null
   const float* beta;   // [COUT] or null (bias when alpha is null)
   const float* res;    // [B,D,Ho,Wo,COUT] or null
@@ -31,7 +29,7 @@ struct LdsConvParams {
   int prefetch_early;                  // 3-D: issue the next plane's loads before (1) or after (0) the MFMA block
   int s2d;                             // 2-D: x is [B,H,W,CIN/4] at TWICE the resolution; the kernel's input is its four parity images as
                                        // channels (py*2+px)*CIN/4 + c (space-to-depth done by the tile fill): a k5 s2 layer as a 3x3 conv
-  // training (ST kernels): per-channel sums of the output in the epilogue, see conv3d.hip ConvParams::stat_mode
+  // training (ST kernels): per-channel sums of the output in the epilogue, see conv3d_common.h ConvParams::stat_mode
   int stat_mode;
   const float* stat_y;
   const float* stat_aux;               // [groups][4*COUT]
@@ -39,20 +37,6 @@ struct LdsConvParams {
   int stat_groups;                     // 2-D: BatchNorm groups (consecutive sets of B / groups images); the ST grid is groups x blocks-per-group
   int stat_slices;                     // slices of stat_out [slices][groups][2C] the blocks are spread over (common.h: conv_stat_send)
 };
-
-// fp64 LDS add and the DPP sum over the 16 lanes that hold the 16 MFMA columns of one 4-channel row group
-__device__ __forceinline__ void lds_add_f64(double* p, double v) { atomicAdd(p, v); }
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov_f(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float row16_sum(float v) {
-  v += dpp_mov_f<0xB1>(v);    // quad_perm [1,0,3,2]
-  v += dpp_mov_f<0x4E>(v);    // quad_perm [2,3,0,1]
-  v += dpp_mov_f<0x141>(v);   // row_half_mirror
-  v += dpp_mov_f<0x140>(v);   // row_mirror
-  return v;
-}
 
 template <int N> struct VecT;
 template <> struct VecT<4> { typedef float4 type; };
@@ -129,7 +113,7 @@ constexpr int round_s(int n, int kpl, int sw) {
 // (three quarters) of every MFMA.  Instead RW = 2 (4) neighbouring output voxels along w share one MFMA column: GEMM row
 // r*Cout + c is channel c of output voxel RW*m + r, which is the same conv written with stride RW, Cout' = RW*Cout and a
 // kernel of KHW + RW - 1 taps along w (tap kw' of phase r is the original tap kw' - r, zero outside) -- KW' taps serve RW
-// outputs instead of RW*KHW: 4 vs 6 (RW 2), 6 vs 12 (RW 4) MFMAs.  The expanded weights are packed by conv3d.hip.
+// outputs instead of RW*KHW: 4 vs 6 (RW 2), 6 vs 12 (RW 4) MFMAs.  The expanded weights are packed by conv_pack.hip.
 //
 // WG = 1 (Winograd form, 3-D stride-1 3x3x3 layers): F(2x2, 3x3) in (h, w), direct in d.  An MFMA column is a 2x2 output
 // tile; per input plane and 16-cin chunk a lane reads its tile's 4x4 patch from LDS, transforms it (B^T d B, 32 adds per
@@ -194,35 +178,6 @@ struct Cfg {
   static constexpr int STAT_OFF = EPI_OFF + 128, SAUX_OFF = STAT_OFF + 256;   // floats (STAT_OFF*4 is a multiple of 8)
   static constexpr size_t LDS_BYTES_ST = LDS_BYTES + 512 * sizeof(float);
 };
-
-// ST epilogue: the lane's 4 output values o[] of channels c0.. at output index oi -> its running sums (ps, pq)
-template <typename C, int ST>
-__device__ __forceinline__ void stat_accum(const LdsConvParams& p, const float* lds_base, size_t oi, int c0, const float (&o)[4],
-                                           float (&ps)[4], float (&pq)[4]) {
-  if constexpr (ST == 1) {     // (the two modes are separate instantiations: together they cost the 2-D kernels an occupancy step)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { ps[k] += o[k]; pq[k] = fmaf(o[k], o[k], pq[k]); }
-  } else {
-    const float* ax = lds_base + C::SAUX_OFF;
-    const float4 yv4 = *reinterpret_cast<const float4*>(p.stat_y + oi);
-    const float yv[4] = {yv4.x, yv4.y, yv4.z, yv4.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float dr = (fmaf(yv[k], ax[c0 + k], ax[64 + c0 + k]) > 0.0f) ? o[k] : 0.0f;
-      ps[k] += dr;
-      pq[k] = fmaf(dr, (yv[k] - ax[128 + c0 + k]) * ax[192 + c0 + k], pq[k]);
-    }
-  }
-}
-template <typename C>
-__device__ __forceinline__ void stat_commit(float* lds_base, int c0, int n16, const float (&ps)[4], const float (&pq)[4]) {
-  double* tab = reinterpret_cast<double*>(lds_base + C::STAT_OFF);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float a1 = row16_sum(ps[k]), a2 = row16_sum(pq[k]);
-    if (n16 == 0) { lds_add_f64(&tab[c0 + k], (double)a1); lds_add_f64(&tab[64 + c0 + k], (double)a2); }
-  }
-}
 
 // The MFMA part of one output row-tile of one depth plane: MTL live m-tiles (16 voxels each) x all GEMM rows, accumulated into
 // acc (zeroed here).  Fully unrolled over the taps: LDS offsets are immediates, no bounds logic (halos are zero-filled in LDS).

@@ -1,4 +1,4 @@
-// The layout of a packed conv weight set, once: what the pack kernels (conv3d.hip) write and where every reader finds its
+// The layout of a packed conv weight set, once: what the pack kernels (conv_pack.hip) write and where every reader finds its
 // segment.  Plain constexpr C++17 with no HIP include, so the pack kernels and a host-only translation unit can both use it.
 #pragma once
 

@@ -174,15 +174,8 @@ int launch_prob_fused_d(ProbParams& p, hipStream_t st) {
   p.tiles_w = (p.W + C::TWO - 1) / C::TWO;
   const long long tiles = (long long)p.B * p.tiles_h * p.tiles_w;
   if (tiles > 0x7fffffff) return mdf::fail(MDF_EARG, "prob head: too many tiles");
-  static bool attr_done_dev[64] = {};   // (per instantiation; the attribute is set to the device maximum once: the size depends on D)
-  int dev_id = 0;
-  (void)hipGetDevice(&dev_id);
-  bool& attr_done = attr_done_dev[(dev_id >= 0 && dev_id < 64) ? dev_id : 0];
-  if (!attr_done || dev_id >= 64) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&prob_fused_kernel<CIN, NW, DT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return mdf::fail(MDF_EHIP, "hipFuncSetAttribute(dynamic LDS): %s", hipGetErrorString(e));
-    attr_done = true;
-  }
+  // (the attribute is set to the device maximum once: the size depends on D)
+  if (int rc = mdf::ensure_dynamic_lds<&prob_fused_kernel<CIN, NW, DT>>(160 * 1024)) return rc;
   hipLaunchKernelGGL((prob_fused_kernel<CIN, NW, DT>), dim3((unsigned)tiles), dim3(C::NTHR), kLds, st, p);
   return mdf::check_launch("prob_fused_kernel");
 }

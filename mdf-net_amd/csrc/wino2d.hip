@@ -11,7 +11,7 @@
 // Per accumulator the MFMA order is conv_lds.hip's (cin chunk, k): the two kernels agree bit for bit.
 //
 // S2D: the 5x5 stride-2 layers of the pyramid (8 -> 16, 16 -> 32; backbone.py:20-27) as a 3x3 stride-1 conv over the FOUR PARITY IMAGES of
-// their input (conv_lds.hip, LdsConvParams::s2d; weights: conv3d.hip kSrcK5S2Phases): 16 instead of 25 MFMA groups per input channel.
+// their input (conv_lds.hip, LdsConvParams::s2d; weights: conv_pack.hip kSrcK5S2Phases): 16 instead of 25 MFMA groups per input channel.
 // x is then [B, 2H, 2W, CIN/4]; cin group g = parity (py*2+px) * (CIN/16) + 4-channel slice, and only the fill's addresses change.
 //   * dead steps (W2Live): a 5-tap row is 3 taps on the even parity and 2 on the odd one, which kSrcK5S2Phases pads to (g0, g1, 0); the last
 //     row of G is [0 0 1], so every transform-domain weight with a == 3 of a py == 1 parity, and with b == 3 of a px == 1 parity, is
@@ -46,7 +46,7 @@ __device__ __forceinline__ void static_for(F&& f) {
 
 struct Wino2dParams {
   const float* x;      // [B,H,W,CIN]; S2D: [B,2H,2W,CIN/4]
-  const float* wpack;  // transform-domain fragments [chunk][ab][nt][lane][4] (conv3d.hip: pack_wino_elem, nkd = 1)
+  const float* wpack;  // transform-domain fragments [chunk][ab][nt][lane][4] (conv_pack.hip: pack_wino_elem, nkd = 1)
   const float* alpha;  // [COUT] or null
   const float* beta;   // [COUT] or null
   const float* res;    // [B,H,W,COUT] or null
@@ -486,16 +486,8 @@ int launch_wino2d(Wino2dParams& p, hipStream_t st) {
   const long long tiles = (long long)p.B * p.tiles_h * p.tiles_w;
   if (tiles >= (1ll << 31)) return MDF_EUNSUPPORTED;
   p.n_tiles = (int)tiles;
-  auto kern = &wino2d_kernel<CIN, COUT, NA, WRITE_AB, S2D, S2D && SKIP, PAD>;
-  static bool attr_done_dev[64] = {};
-  int dev_id = 0;
-  (void)hipGetDevice(&dev_id);
-  bool& attr_done = attr_done_dev[(dev_id >= 0 && dev_id < 64) ? dev_id : 0];
-  if (!attr_done || dev_id >= 64) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
-    if (e != hipSuccess) return mdf::fail(MDF_EHIP, "hipFuncSetAttribute(dynamic LDS %zu): %s", (size_t)C::LDS_BYTES, hipGetErrorString(e));
-    attr_done = true;
-  }
+  constexpr auto kern = &wino2d_kernel<CIN, COUT, NA, WRITE_AB, S2D, S2D && SKIP, PAD>;
+  if (int rc = mdf::ensure_dynamic_lds<kern>(C::LDS_BYTES)) return rc;
   long long grid = 256;      // one block per CU
   grid = mdf::env_pos("MDF_WINO2D_GRID", grid);   // dev
   if (grid > tiles / 2) grid = tiles / 2;

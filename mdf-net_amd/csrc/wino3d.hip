@@ -33,7 +33,7 @@ __device__ __forceinline__ void static_for(F&& f) {
 
 struct Wino3dParams {
   const float* x;      // [B,D,H,W,CIN]
-  const float* wpack;  // transform-domain fragments [kd][chunk][ab][nt][lane][4] (conv3d.hip: pack_wino_elem)
+  const float* wpack;  // transform-domain fragments [kd][chunk][ab][nt][lane][4] (conv_pack.hip: pack_wino_elem)
   const float* alpha;  // [COUT] or null
   const float* beta;   // [COUT] or null
   const float* res;    // [B,D,H,W,COUT] or null
@@ -412,16 +412,8 @@ int launch_wino3d(Wino3dParams& p, hipStream_t st) {
   p.tiles_w = (p.W + C::TWO - 1) / C::TWO;
   p.total = (long long)p.B * p.tiles_h * p.tiles_w * p.D;
   if (p.total >= (1ll << 31)) return MDF_EUNSUPPORTED;
-  auto kern = &wino3d_kernel<CIN, COUT, NA, WRITE_AB>;
-  static bool attr_done_dev[64] = {};
-  int dev_id = 0;
-  (void)hipGetDevice(&dev_id);
-  bool& attr_done = attr_done_dev[(dev_id >= 0 && dev_id < 64) ? dev_id : 0];
-  if (!attr_done || dev_id >= 64) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
-    if (e != hipSuccess) return mdf::fail(MDF_EHIP, "hipFuncSetAttribute(dynamic LDS %zu): %s", (size_t)C::LDS_BYTES, hipGetErrorString(e));
-    attr_done = true;
-  }
+  constexpr auto kern = &wino3d_kernel<CIN, COUT, NA, WRITE_AB>;
+  if (int rc = mdf::ensure_dynamic_lds<kern>(C::LDS_BYTES)) return rc;
   // one block per CU (192 accumulator registers per lane); every block at least ~4 planes so that a segment's two halo planes stay a fraction
   long long grid = 256;
   grid = mdf::env_pos("MDF_WINO3D_GRID", grid);   // dev
