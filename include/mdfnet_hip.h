@@ -241,6 +241,20 @@ int mdf_hypos_fit_fwd(int mode, const float* prob, const float* depth, const flo
 int mdf_hypos_from_fit_fwd(int mode, const float* s, const float* depth, const float* range, float log_thresh,
                            float* hypos_out, int B, int D_out, int h, int w, int upsample, void* stream);
 
+/* ---- a3''' atv_hypos (net/unit/depthhypos.py:218-253): the adaptive-thin-volume range of UCS-Net, the baseline the curve fits
+ *      are compared with; HyposByFit's fourth curve, "atv".
+ * mdf_atv_spread_fwd: spread [B,h,w] = scale * sqrt(sum_d prob_d (hypos_d - depth)^2), the exp_variance atv_hypos takes (nothing
+ *      in the reference computes it).  prob [B,D,h,w]; depth [B,h,w]; hypos as above; scale finite and > 0 (UCS-Net: 1.5).
+ *      Held to the formula in float64 on the same inputs: (D/2 + 4) * 2^-24 relative; a sum of exact zeros gives exactly 0.
+ * mdf_atv_hypos_fwd: e2, d2 = bilinear x2 of spread, depth (align_corners=False; upsample == 0: the maps as they are);
+ *      low = -min(d2, e2); step = (e2 - low) / (D_out - 1); hypos_out[i] = ((d2 + low) + step * i) + 1e-12 -> [B,D_out,2h,2w]
+ *      (or [B,D_out,h,w]), the reference's fp32 bits.  D_out >= 2.  NOT clamped to the depth range (the reference has no
+ *      clamp): the hypotheses can leave [depth_min, depth_max]; every one is >= 1e-12.                                     */
+int mdf_atv_spread_fwd(const float* prob, const float* depth, const float* hypos, int hypos_per_pixel, float scale,
+                       float* spread_out, int B, int D, int h, int w, void* stream);
+int mdf_atv_hypos_fwd(const float* spread, const float* depth, float* hypos_out, int B, int D_out, int h, int w, int upsample,
+                      void* stream);
+
 /* ---- N1  depth-map consistency filter + fusion (tools/filter/dynamic_filter_gpu.py:63-103,166-238) ----------
  * One fused pass over a reference view and its n_src source views: reprojection, bilinear depth gather, the nine
  * dynamic thresholds (dist < i/thre1, rel < i/thre2, i = 2..10), geo = #(count_i >= i) >= nconditions,

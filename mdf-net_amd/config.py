@@ -167,7 +167,8 @@ ngroups = (32, 16, 8)
 
 
 AGGREGATES = ("vector", "variance")
-CURVES = ("gauss0", "gauss1", "laplace")
+CURVES = ("gauss0", "gauss1", "laplace", "atv")
+atv_scale = (1.5, 1.5)               # UCS-Net's lamb, for a stage whose curve is "atv"
 CONFIDENCES = ("last", "cascade")
 
 
@@ -194,9 +195,23 @@ def _curve_args(curves, thresh):
     return [None] + list(curves), [0.0] + [float(t) for t in thresh]
 
 
-def build_model(aggregate="vector", curves=None, prob_thresh=None, confidence="last"):
+def _atv_args(scales):
+    """-> per-stage atv_scale list of the three HyposByFit slots, checked (read only by a slot whose curve is "atv")."""
+    scales = atv_scale if scales is None else scales
+    try:
+        scales = tuple(float(v) for v in scales)
+    except TypeError:
+        raise ValueError(f"atv_scale={scales!r}: a pair (stage 1, stage 2)") from None
+    if len(scales) != 2 or not all(0.0 < v < float("inf") for v in scales):
+        raise ValueError(f"atv_scale={scales!r}: a pair (stage 1, stage 2) of finite values greater than 0")
+    return [1.5] + list(scales)
+
+
+def build_model(aggregate="vector", curves=None, prob_thresh=None, confidence="last", atv_scale=None):
     """A fresh CoreNet.  curves: the curve HyposByFit fits before stages 1 and 2, default ("gauss1", "laplace"); prob_thresh: their
-    thresholds, default (0.95, 1e-5).  Every choice has the same state_dict (the slot has no parameters), so one checkpoint loads
+    thresholds, default (0.95, 1e-5).  "atv" in a stage is the adaptive-thin-volume range of the reference's atv_hypos instead of a
+    curve fit: it reads atv_scale (a pair, default (1.5, 1.5), each finite and > 0) and ignores its prob_thresh (still checked); its
+    hypotheses are not clamped to the depth range.  Every choice has the same state_dict (the slot has no parameters), so one checkpoint loads
     into all of them; which curves it was trained with is the caller's to keep.  aggregate="vector" (default): composed exactly like the reference's singleton.  aggregate="variance":
     the classic MVSNet variance cost volume in the Homoaggre slots (homo_aggregate_by_variance, homoaggregate.py:49-69), whose
     cost volume has the C = 2 G feature channels, so the regularisers' first layers are 64->16, 32->8, 16->8.  That model has no
@@ -210,7 +225,8 @@ def build_model(aggregate="vector", curves=None, prob_thresh=None, confidence="l
     if confidence not in CONFIDENCES:
         raise ValueError(f"confidence={confidence!r}: choose one of {CONFIDENCES}")
     cv, th = _curve_args(curves, prob_thresh)
-    hypos = nn.ModuleList([HyposByFit(ndepths[i], cv[i], th[i]) for i in range(stages - 1)])
+    sc = _atv_args(atv_scale)
+    hypos = nn.ModuleList([HyposByFit(ndepths[i], cv[i], th[i], atv_scale=sc[i]) for i in range(stages - 1)])
     if aggregate == "variance":
         from net.unit.homoaggregate import homo_aggregate_by_variance
         aggre = [homo_aggregate_by_variance] * (stages - 1)

@@ -438,6 +438,76 @@ __global__ void hypos_from_fit_kernel(int mode, const float* __restrict__ s, con
   }
 }
 
+// ---- the adaptive-thin-volume range (depthhypos.py:218-253, UCS-Net's baseline the curve fits are compared with) ----
+// Spread of the previous stage's distribution around its regressed depth: e = scale * sqrt(sum_d p_d (x_d - depth)^2), the
+// exp_variance that atv_hypos takes.  Nothing in the reference computes it, so there are no bits to mirror: the sum runs in four
+// interleaved fma accumulators (Sum4) and is held to the formula in float64, (D/2 + 4) * 2^-24 relative.  The probabilities are
+// summed as p * 2^64 and the root scaled back by 2^-32, both exact: a softmax's denormal tails times a squared distance of a few
+// millimetres would otherwise round in the denormal range, where the error is absolute.  A sum of exact zeros (p = 0 everywhere,
+// or a one-hot p on a hypothesis equal to the depth) gives exactly 0.  Same traffic as hypos_curve_fit_kernel's mode 3.
+template <int DT>
+__global__ __launch_bounds__(kThreads) void atv_spread_kernel(const float* __restrict__ prob, const float* __restrict__ depth,
+                                                              const float* __restrict__ hypos, int per_pixel, float scale,
+                                                              float* __restrict__ e_out, int B, int D_rt, int hw) {
+  const int D = DT ? DT : D_rt;
+  const size_t n = (size_t)B * hw;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t b = i / hw, pix = i % hw;
+    const float* p = prob + b * D * hw + pix;
+    const float dep = depth[i];
+    Sum4 acc;
+    if constexpr (DT != 0) {
+      float pv[DT], xv[DT];
+#pragma unroll
+      for (int d = 0; d < DT; ++d) { pv[d] = p[(size_t)d * hw]; xv[d] = hyp_at(hypos, per_pixel, b, D, d, hw, pix); }
+#pragma unroll
+      for (int d = 0; d < DT; ++d) {
+        const float t = xv[d] - dep;
+        acc.fma(d, ldexpf(pv[d], 64), t * t);
+      }
+    } else {
+      for (int d = 0; d < D; ++d) {
+        const float t = hyp_at(hypos, per_pixel, b, D, d, hw, pix) - dep;
+        acc.fma(d, ldexpf(p[(size_t)d * hw], 64), t * t);
+      }
+    }
+    e_out[i] = scale * ldexpf(sqrtf(acc.result()), -32);
+  }
+}
+
+// depthhypos.py:239-253 with the depth upsampled as HyposByFit does it (:51).  One thread per OUTPUT pixel, D_out coalesced planes:
+//   low = -min(d2, e2);  step = (e2 - low) / (D_out - 1);  hyp_i = ((d2 + low) + step * i) + 1e-12
+// torch's operations one by one, each rounded on its own (no fma: the reference has none); torch.min hands on a NaN of either side.
+// No clamp to the depth range: the reference has none, the lower bound keeps every hypothesis >= 1e-12.
+__global__ void atv_hypos_kernel(const float* __restrict__ e, const float* __restrict__ depth, float* __restrict__ out, int B,
+                                 int D_out, int h, int w, int upsample) {
+  const int Ho = upsample ? 2 * h : h, Wo = upsample ? 2 * w : w;
+  const size_t ohw = (size_t)Ho * Wo, n = (size_t)B * ohw;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t b = i / ohw;
+    float ev, dv;
+    if (upsample) {
+      const int oy = (int)((i % ohw) / Wo), ox = (int)(i % Wo);
+      int y0, y1, x0, x1;
+      float ly0, ly1, lx0, lx1;
+      up2_coord(oy, h, y0, y1, ly0, ly1);
+      up2_coord(ox, w, x0, x1, lx0, lx1);
+      ev = up2_sample(e + b * h * w, w, y0, y1, x0, x1, ly0, ly1, lx0, lx1);
+      dv = up2_sample(depth + b * h * w, w, y0, y1, x0, x1, ly0, ly1, lx0, lx1);
+    } else {
+      ev = e[i];
+      dv = depth[i];
+    }
+    float m = dv < ev ? dv : ev;                                                          // :243
+    m = ev != ev ? ev : (dv != dv ? dv : m);
+    const float low = -m;
+    const float step = __fdiv_rn(__fsub_rn(ev, low), (float)(D_out - 1));                 // :245
+    const float base = __fadd_rn(dv, low);                                                // :249
+    for (int k = 0; k < D_out; ++k)
+      out[(b * D_out + k) * ohw + (i % ohw)] = __fadd_rn(__fadd_rn(base, __fmul_rn(step, (float)k)), 1e-12f);
+  }
+}
+
 // One thread per pixel: at 1/8 resolution (148 x 200) that is 29,600 threads -- 116 blocks of 256 on 256 CUs, i.e. 140 CUs idle and
 // four waves on each of the others.  Small problems therefore go out as one-wave blocks, which the dispatcher spreads over all CUs
 // (the kernels index with blockDim.x; nothing in them is block-cooperative).
@@ -537,4 +607,28 @@ extern "C" int mdf_hypos_from_fit_fwd(int mode, const float* s, const float* dep
   hipLaunchKernelGGL(hypos_from_fit_kernel, dim3(grid_for(n)), dim3(block_for(n)), 0, (hipStream_t)stream, mode, s, depth,
                      range, log_thresh, hypos_out, B, D_out, h, w, upsample);
   return mdf::check_launch("hypos_from_fit_kernel");
+}
+
+extern "C" int mdf_atv_spread_fwd(const float* prob, const float* depth, const float* hypos, int hypos_per_pixel, float scale,
+                                  float* spread_out, int B, int D, int h, int w, void* stream) {
+  MDF_REQUIRE(prob && depth && hypos && spread_out, "null pointer argument");
+  MDF_REQUIRE(B > 0 && D > 0 && h > 0 && w > 0, "bad shape");
+  MDF_REQUIRE(scale > 0.0f && scale <= 3.402823466e38f, "scale must be finite and positive, got %g", (double)scale);
+  const size_t px = (size_t)B * h * w;
+#define MDF_AS(DT) hipLaunchKernelGGL(atv_spread_kernel<DT>, dim3(grid_for(px)), dim3(block_for(px)), 0, (hipStream_t)stream, prob, depth, \
+                                      hypos, hypos_per_pixel, scale, spread_out, B, D, h * w)
+  if (D == 48) MDF_AS(48); else if (D == 24) MDF_AS(24); else if (D == 8) MDF_AS(8); else MDF_AS(0);
+#undef MDF_AS
+  return mdf::check_launch("atv_spread_kernel");
+}
+
+extern "C" int mdf_atv_hypos_fwd(const float* spread, const float* depth, float* hypos_out, int B, int D_out, int h, int w,
+                                 int upsample, void* stream) {
+  MDF_REQUIRE(spread && depth && hypos_out, "null pointer argument");
+  MDF_REQUIRE(B > 0 && h > 0 && w > 0, "bad shape");
+  MDF_REQUIRE(D_out >= 2, "D_out must be at least 2 (the step divides by D_out - 1), got %d", D_out);
+  const size_t n = (size_t)B * h * w * (upsample ? 4 : 1);
+  hipLaunchKernelGGL(atv_hypos_kernel, dim3(grid_for(n)), dim3(block_for(n)), 0, (hipStream_t)stream, spread, depth, hypos_out, B,
+                     D_out, h, w, upsample ? 1 : 0);
+  return mdf::check_launch("atv_hypos_kernel");
 }

@@ -105,8 +105,10 @@ def main():
     parser.add_argument("--aggregate", default="vector", type=str, choices=list(config.AGGREGATES),
                         help="cost-volume operator the checkpoint was trained with (train.py --aggregate)")
     parser.add_argument("--curves", default="gauss1,laplace", type=str,
-                        help="hypothesis curves the checkpoint was trained with (train.py --curves): two of gauss0, gauss1, laplace")
+                        help="hypothesis curves the checkpoint was trained with (train.py --curves): two of gauss0, gauss1, laplace, atv")
     parser.add_argument("--prob_thresh", default="0.95,1e-5", type=str, help="their probability thresholds, each inside (0, 1)")
+    parser.add_argument("--atv_scale", default="1.5,1.5", type=str,
+                        help="scale of the spread for a stage whose curve is atv (UCS-Net's lamb), each finite and > 0")
     parser.add_argument("--confidence", default="last", type=str, choices=list(config.CONFIDENCES),
                         help="last: confidence of the last stage's probability volume (the reference's composition); cascade: every stage "
                              "blends 0.8 x the bicubic x2 of the previous stage's confidence with 0.2 x its own (any checkpoint loads)")
@@ -133,9 +135,10 @@ def main():
         from load.tankseval import LoadDataset
         dataset = LoadDataset(datasetpath=load_args.eval_root, scenelist=load_args.scenelist, nviews=eval_args.nviews)
     curves, thresh = config.parse_pair(args.curves, str), config.parse_pair(args.prob_thresh, float)
+    atv_scale = config.parse_pair(args.atv_scale, float)
     default = args.aggregate == "vector" and curves == tuple(config.curve_calss[1:]) and thresh == tuple(config.prob_thresh[1:]) \
         and args.confidence == "last"
-    model = config.model if default else config.build_model(aggregate=args.aggregate, curves=curves, prob_thresh=thresh,
+    model = config.model if default else config.build_model(aggregate=args.aggregate, curves=curves, prob_thresh=thresh, atv_scale=atv_scale,
                                                             confidence=args.confidence)
     if args.pre_model is not None:
         model.load_state_dict(torch.load(args.pre_model, map_location="cpu")["model"])

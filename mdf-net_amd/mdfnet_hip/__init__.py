@@ -141,6 +141,8 @@ SIGNATURES = {
     "mdf_adam_step": (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_fp] + [ctypes.c_float] * 5 + [c_i64, c_fp]),
     "mdf_adam_step_hyper": (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_fp] + [ctypes.c_float] * 4 + [c_fp]),
     "mdf_hypos_from_fit_fwd": (c_int, [c_int, c_fp, c_fp, c_fp, ctypes.c_float, c_fp] + [c_int] * 5 + [c_fp]),
+    "mdf_atv_spread_fwd": (c_int, [c_fp, c_fp, c_fp, c_int, ctypes.c_float, c_fp] + [c_int] * 4 + [c_fp]),
+    "mdf_atv_hypos_fwd": (c_int, [c_fp, c_fp, c_fp] + [c_int] * 5 + [c_fp]),
 }
 
 

@@ -480,6 +480,34 @@ def hypos_from_fit(mode, s, depth, depth_range_f32, log_thresh, ndepths, upsampl
     return out
 
 
+def atv_spread(prob, depth, depth_hypos, scale=1.5):
+    """Step 1 of the "atv" curve: e = scale * sqrt(sum_d prob_d (hypos_d - depth)^2) [B,h,w], UCS-Net's exp_variance (the second
+    argument of the reference's atv_hypos, depthhypos.py:218).  Hypotheses [B,D,1,1] or [B,D,h,w]; scale finite and > 0."""
+    _need_gpu(prob, depth)
+    b, d, h, w = prob.shape
+    if tuple(depth.shape) != (b, h, w) or tuple(depth_hypos.shape[:2]) != (b, d):
+        raise ValueError(f"atv_spread: prob {tuple(prob.shape)} needs depth [B,h,w] and hypos [B,D,..], got {tuple(depth.shape)}, {tuple(depth_hypos.shape)}")
+    prob_c, depth_c = _f32c(prob), _f32c(depth)      # (locals: as in hypos_fit)
+    hyp, pp = _hypos_arg(depth_hypos, h, w)
+    out = torch.empty((b, h, w), device=prob.device, dtype=torch.float32)
+    _abi("mdf_atv_spread_fwd", (prob_c.data_ptr(), depth_c.data_ptr(), hyp.data_ptr(), pp, ctypes.c_float(scale), out.data_ptr(),
+                                b, d, h, w, _stream(out),))
+    return out
+
+
+def atv_hypos(spread, depth, ndepths, upsample=True):
+    """Step 2 of the "atv" curve (depthhypos.py:239-253) -> [B,D,2h,2w] (or [B,D,h,w]).  Not clamped to the depth range."""
+    _need_gpu(spread, depth)
+    b, h, w = spread.shape
+    if depth.shape != spread.shape:
+        raise ValueError(f"atv_hypos: spread {tuple(spread.shape)} and depth {tuple(depth.shape)} must have one shape")
+    ho, wo = (2 * h, 2 * w) if upsample else (h, w)
+    out = torch.empty((b, max(int(ndepths), 0), ho, wo), device=spread.device, dtype=torch.float32)
+    spread_c, depth_c = _f32c(spread), _f32c(depth)
+    _abi("mdf_atv_hypos_fwd", (spread_c.data_ptr(), depth_c.data_ptr(), out.data_ptr(), b, ndepths, h, w, int(upsample), _stream(out),))
+    return out
+
+
 # --------------------------------------------------------------------------- 3-D conv layers (NDHWC)
 def to_ndhwc(t):
     """logical [B,C,D,H,W] -> contiguous [B,D,H,W,C] tensor (no copy when the memory already is)."""

@@ -1,10 +1,10 @@
-"""Depth-hypothesis slot (reference: net/unit/depthhypos.py:10-215)."""
+"""Depth-hypothesis slot (reference: net/unit/depthhypos.py:10-253)."""
 import torch
 import torch.nn as nn
 
 from mdfnet_hip import controlplane, hostmirror, layers, ops
 
-CURVES = ("gauss0", "gauss1", "laplace")
+CURVES = ("gauss0", "gauss1", "laplace", "atv")
 _STEP2 = {"gauss0": 1, "gauss1": 1, "laplace": 2}     # mdf_hypos_from_fit_fwd: sqrt(-s ln thr) for both Gaussians, |s ln thr|
 
 
@@ -17,6 +17,8 @@ def fit_mode(curve, per_pixel):
         return 4 if per_pixel else 1
     if curve == "laplace":
         return 2
+    if curve == "atv":
+        return None                                   # no fit: the spread kernel (mdf_atv_spread_fwd) takes its place
     raise NotImplementedError(f"HyposByFit curve '{curve}' is not built ({', '.join(CURVES)} are)")
 
 
@@ -24,13 +26,18 @@ class HyposByFit(nn.Module):
     """HyposByFit(ndepths, curve_calss, prob_thresh); no parameters or buffers (contributes nothing to
     the state_dict, like the reference whose prob_thresh is a plain tensor attribute).
 
+    curve_calss "atv" is the reference's atv_hypos (depthhypos.py:218-253) in this slot: the range is the spread
+    atv_scale * sqrt(sum_d p_d (x_d - depth)^2) of the previous stage's distribution (UCS-Net's exp_variance with lamb = atv_scale)
+    on either side of the depth, not a curve fit; prob_thresh is ignored, nothing comes from the host, and the hypotheses are not
+    clamped to the depth range (the reference has no clamp; every hypothesis is >= 1e-12).
+
     ops.recorded("log_thresh", step-2 mode) hands out the logarithms recorded for the pinned goldens of the default composition.
     It is keyed by the step-2 mode, which two Gaussian stages with different thresholds would share, so only a slot with one of
     the default composition's (curve, threshold) pairs consults it; every other takes log(prob_thresh)."""
 
-    def __init__(self, ndepths: int = 16, curve_calss: str = "gauss1", prob_thresh: float = 0.95) -> None:
+    def __init__(self, ndepths: int = 16, curve_calss: str = "gauss1", prob_thresh: float = 0.95, atv_scale: float = 1.5) -> None:
         super().__init__()
-        self.ndepths, self.curve_calss = ndepths, curve_calss
+        self.ndepths, self.curve_calss, self.atv_scale = ndepths, curve_calss, float(atv_scale)
         self.prob_thresh = torch.tensor(prob_thresh)
         self.default_curve = (curve_calss, float(prob_thresh)) in (("gauss1", 0.95), ("laplace", 1e-5))     # config.py:147-148
 
@@ -57,8 +64,15 @@ class HyposByFit(nn.Module):
         mode = fit_mode(self.curve_calss, depth_hypos.shape[-1] != 1 or depth_hypos.shape[-2] != 1)
         on_gpu = depth.is_cuda and prob_volume.is_cuda      # no gradient flows here (depthhypos.py:40): same kernels in training
         if not on_gpu and not layers.use_hip(self, depth.detach(), prob_volume.detach()):
+            if self.curve_calss == "atv":
+                return layers.stock().hypos_by_atv(self.atv_scale, self.ndepths, depth.detach(), prob_volume.detach(),
+                                                   depth_hypos.detach(), upsample)
             return layers.stock().hypos_by_fit(self.curve_calss, self.prob_thresh, self.ndepths, depth.detach(), depth_range,
                                          prob_volume.detach(), depth_hypos.detach(), upsample)
+        if self.curve_calss == "atv":
+            with torch.no_grad():
+                e = ops.atv_spread(prob_volume, depth, depth_hypos, self.atv_scale)
+                return ops.atv_hypos(e, depth, self.ndepths, bool(upsample))
         step2 = _STEP2[self.curve_calss]
         with torch.no_grad():
             row = None

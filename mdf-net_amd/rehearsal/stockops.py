@@ -132,7 +132,7 @@ def _fit(curve, depth, prob, hypos):
         return _fit_gauss1(prob, hypos) if hypos.shape[-1] == 1 and hypos.shape[-2] == 1 else _fit_gauss1_centred(prob, hypos)
     if curve == "laplace":
         return _fit_laplace(depth, prob, hypos)
-    raise NotImplementedError(f"HyposByFit curve '{curve}' is not built (gauss0, gauss1, laplace are)")
+    raise NotImplementedError(f"HyposByFit curve '{curve}' is not built (gauss0, gauss1, laplace, atv are)")
 
 
 def hypos_by_fit(curve, prob_thresh, ndepths, depth, depth_range, prob, hypos, upsample):
@@ -154,3 +154,21 @@ def hypos_by_fit(curve, prob_thresh, ndepths, depth, depth_range, prob, hypos, u
         lo4, hi4 = lo.reshape(b, 1, 1, 1), hi.reshape(b, 1, 1, 1)
         hyp = lo4 + (hyp - lo4).clamp(min=0)
         return hi4 + (hyp - hi4).clamp(max=0)
+
+
+def atv_spread(scale, depth, prob, hypos):
+    """UCS-Net's exp_variance, the second argument of atv_hypos: scale * sqrt(sum_d p_d (x_d - depth)^2)."""
+    return scale * torch.sqrt(torch.sum(prob * (hypos - depth.unsqueeze(1)) ** 2, 1))
+
+
+def hypos_by_atv(scale, ndepths, depth, prob, hypos, upsample):
+    """HyposByFit.forward with curve "atv" for depth is not None: depthhypos.py:239-253 on the spread above, the depth upsampled as
+    HyposByFit does it (:51).  Not clamped to the depth range (the reference has no clamp)."""
+    with torch.no_grad():
+        e = atv_spread(scale, depth, prob, hypos)
+        if upsample:
+            e = F.interpolate(e.unsqueeze(1), scale_factor=2, mode="bilinear").squeeze(1)
+            depth = F.interpolate(depth.unsqueeze(1), scale_factor=2, mode="bilinear").squeeze(1)
+        low = -torch.min(depth, e)
+        step = (e - low) / (ndepths - 1)
+        return torch.stack([depth + low + step * k + 1e-12 for k in range(ndepths)], dim=1)

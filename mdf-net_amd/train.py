@@ -75,8 +75,10 @@ def build_parser():
     parser.add_argument("--aggregate", default="vector", type=str, choices=list(config.AGGREGATES),
                         help="cost-volume operator of the Homoaggre slots: the reference's VectorAggregate, or the variance cost volume")
     parser.add_argument("--curves", default="gauss1,laplace", type=str,
-                        help="hypothesis curves fitted before stages 1 and 2: two of gauss0, gauss1, laplace")
+                        help="hypothesis curves fitted before stages 1 and 2: two of gauss0, gauss1, laplace, atv")
     parser.add_argument("--prob_thresh", default="0.95,1e-5", type=str, help="their probability thresholds, each inside (0, 1)")
+    parser.add_argument("--atv_scale", default="1.5,1.5", type=str,
+                        help="scale of the spread for a stage whose curve is atv (UCS-Net's lamb), each finite and > 0")
     parser.add_argument("--val_every", default=0, type=int,
                         help="validate every N epochs on the dataset's validation items (validate.py; one line per validation in "
                              "<pth>/epoch_val.txt); 0 (default): never")
@@ -128,8 +130,9 @@ def main():
                          "CPU rehearsal")
     val_set = make_val_dataset(args, train_args.nviews)
     curves, thresh = config.parse_pair(args.curves, str), config.parse_pair(args.prob_thresh, float)
+    atv_scale = config.parse_pair(args.atv_scale, float)
     default = args.aggregate == "vector" and curves == tuple(config.curve_calss[1:]) and thresh == tuple(config.prob_thresh[1:])
-    model = config.model if default else config.build_model(aggregate=args.aggregate, curves=curves, prob_thresh=thresh)
+    model = config.model if default else config.build_model(aggregate=args.aggregate, curves=curves, prob_thresh=thresh, atv_scale=atv_scale)
     start_epoch = train_args.start_epoch
     if args.pre_model is not None:
         ckpt = torch.load(args.pre_model, map_location="cpu")

@@ -24,8 +24,10 @@ def build_parser():
     parser.add_argument("--aggregate", default="vector", type=str, choices=list(config.AGGREGATES),
                         help="cost-volume operator the checkpoint was trained with (train.py --aggregate)")
     parser.add_argument("--curves", default="gauss1,laplace", type=str,
-                        help="hypothesis curves fitted before stages 1 and 2: two of gauss0, gauss1, laplace")
+                        help="hypothesis curves fitted before stages 1 and 2: two of gauss0, gauss1, laplace, atv")
     parser.add_argument("--prob_thresh", default="0.95,1e-5", type=str, help="their probability thresholds, each inside (0, 1)")
+    parser.add_argument("--atv_scale", default="1.5,1.5", type=str,
+                        help="scale of the spread for a stage whose curve is atv (UCS-Net's lamb), each finite and > 0")
     parser.add_argument("--confidence", default="last", type=str, choices=list(config.CONFIDENCES),
                         help="which confidence map the confidence table is made of (eval.py --confidence)")
     parser.add_argument("--thresholds", default=None, type=str,
@@ -75,9 +77,10 @@ def main(argv=None):
     eval_args = config.EvalDTU()
     dataset = val_dataset(args.dataset, eval_args.nviews)
     curves, thresh = config.parse_pair(args.curves, str), config.parse_pair(args.prob_thresh, float)
+    atv_scale = config.parse_pair(args.atv_scale, float)
     default = args.aggregate == "vector" and curves == tuple(config.curve_calss[1:]) and thresh == tuple(config.prob_thresh[1:]) \
         and args.confidence == "last"
-    model = config.model if default else config.build_model(aggregate=args.aggregate, curves=curves, prob_thresh=thresh,
+    model = config.model if default else config.build_model(aggregate=args.aggregate, curves=curves, prob_thresh=thresh, atv_scale=atv_scale,
                                                             confidence=args.confidence)
     if args.pre_model is not None:
         model.load_state_dict(torch.load(args.pre_model, map_location="cpu")["model"])
@@ -86,7 +89,7 @@ def main(argv=None):
     rep, _ = valmetrics.run_validation(model, dataset, device, thresholds, relative, rank, world, eval_args.nworks)
     if rank == 0:
         rep["options"] = {"dataset": args.dataset, "checkpoint": args.pre_model, "aggregate": args.aggregate, "curves": list(curves),
-                          "prob_thresh": list(thresh), "confidence": args.confidence}
+                          "prob_thresh": list(thresh), "atv_scale": list(atv_scale), "confidence": args.confidence}
         text = valmetrics.format_report(rep)
         print(text)
         out = args.out or os.path.join(eval_args.output_path, "validation_{}.json".format(args.dataset))
