@@ -13,7 +13,9 @@
 //   * the work is cut stream-K style: block b owns steps [b T / G, (b+1) T / G) of the T = tiles x D (tile, plane) steps in
 //     depth-fastest order -- one round, equal length, at most two tile changes per block, no scheduling atomics;
 //   * plane fill: the thread's global offsets and LDS addresses are lane constants of a tile (buffer loads with an out-of-range
-//     offset for halo voxels, zero planes through num_records = 0): no address arithmetic per plane.
+//     offset for halo voxels, zero planes through num_records = 0): no address arithmetic per plane;
+//   * a last tile column with at most 8 live columns (W = 200: 8 of 32) is covered by strip tiles of 32 rows x 8 columns, whose patch
+//     has the positions of the ordinary one transposed: 5 instead of 19 tiles per image at H = 148, the same products per output.
 // Per accumulator the MFMA order is that of conv_lds.hip's form (kd, cin chunk, k), so the two kernels agree bit for bit.
 #include <cstdlib>
 #include <type_traits>
@@ -40,8 +42,10 @@ struct Wino3dParams {
   float* y;            // [B,D,H,W,COUT]
   float res_scale;
   int B, D, H, W, relu;
-  int tiles_h, tiles_w;
-  long long total;     // B * tiles_h * tiles_w * D steps (< 2^31)
+  int tiles_h, tiles_w;   // ordinary tiles (TH x TWO) per image; with strip tiles tiles_w counts the full tile columns only
+  int strips_h;        // strip tiles (STH x STW, the partly filled last tile column) per image, 0 = none
+  int n_ord;           // B * tiles_h * tiles_w: the strip tiles are numbered behind all ordinary tiles of the launch
+  long long total;     // (n_ord + B * strips_h) * D steps (< 2^31)
 };
 
 template <int CIN, int COUT>
@@ -52,6 +56,11 @@ struct W3 {
   static constexpr int TH = 2 * WM, TWO = 32;       // output tile
   static constexpr int PH = TH + 2, PW = TWO + 2;   // input patch
   static constexpr int NPP = PH * PW;
+  // strip tile for a last tile column with 1 .. STW live columns: the patch transposed (PW x PH positions = NPP again, so the plane
+  // layout, the ring and the fill's LDS addresses are those of the ordinary tile; only position <-> (row, column) differs).  A wave owns
+  // 4 row pairs x 4 column pairs instead of 1 x 16.
+  static constexpr int STH = TWO, STW = TH, SPW = STW + 2;
+  static_assert(NT == 1 && (STH + 2) * SPW == NPP, "strip tiles: one cout tile per wave, the transposed patch");
   static constexpr int S = round_s(NPP, 4, 2);      // vectors per cin group (conv_lds_common.h: bank-conflict-free for the stride-2 patch reads)
   static constexpr int PLANE = CIN * S;             // floats
   static constexpr int RING = 3;
@@ -60,7 +69,10 @@ struct W3 {
   static constexpr int EPI_OFF = RING * PLANE;      // alpha[64], beta[64]
   // the weight fragments of kd slices 0 .. WL-1 stay in LDS for the whole kernel where they fit beside the planes (16 input channels:
   // 48 KB): as buffer loads the fragments are 88 % of the vector-L1 accesses of the kernel (52 M lines per launch of the 32 -> 16
-  // layer, TCP_TOTAL_CACHE_ACCESSES) and keep that path ~half busy, which costs 9-12 % of the run time (ablation, profiles/r05_wino3d.md)
+  // layer, TCP_TOTAL_CACHE_ACCESSES) and keep that path ~half busy, which costs 9-12 % of the run time (ablation, profiles/r05_wino3d.md).
+  // 32 input channels: ONE slice (32 KB) fits exactly with S = NPP + 1 and a table of 2 COUT floats; built and measured, bit-identical and
+  // 17 us SLOWER on the 32 -> 16 layer (219 -> 236 us; suspected, not measured: S % 8 == 5 gives up the conflict-free fill stores), so WL stays all-or-nothing
+  // (profiles/r08_wino3d_strip.md)
   static constexpr int FRAG = 64 * 4;               // floats per fragment
   static constexpr int WL = ((size_t)(RING * PLANE + 128 + 3 * NCH * 16 * NT * FRAG) * sizeof(float) <= 160 * 1024) ? 3 : 0;
   static constexpr int W_OFF = EPI_OFF + 128;
@@ -86,7 +98,7 @@ struct W3 {
 template <int CIN, int COUT, int NA, int WRITE_AB>
 __global__ __launch_bounds__(256, 1) void wino3d_kernel(const Wino3dParams p) {
   typedef W3<CIN, COUT> C;
-  constexpr int NCH = C::NCH, NT = C::NT, S = C::S, PW = C::PW, NPP = C::NPP, NFILL = C::NFILL;
+  constexpr int NCH = C::NCH, NT = C::NT, S = C::S, NPP = C::NPP, NFILL = C::NFILL;
   constexpr int AH = NA - 1;                         // weight fragments run AH ab-steps ahead of their MFMAs
   constexpr int NSTEP = NCH * 16;                    // ab-steps per plane
   static_assert(NSTEP % NA == 0, "the fragment ring must close over a plane");
@@ -94,12 +106,9 @@ __global__ __launch_bounds__(256, 1) void wino3d_kernel(const Wino3dParams p) {
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int q = lane >> 4, n16 = lane & 15;
   const int wm = wave / NT, wn = wave % NT;
   const __amdgpu_buffer_rsrc_t wres = make_rsrc(p.wpack, (unsigned)(3 * NCH * 16 * NT * 64 * 4 * 4));
   const int wvoff = lane * 16;
-  // lane-constant part of the patch-read address (floats): cin group q of the chunk, rows 2 wm .., columns 2 n16 ..
-  const int lane_lds = (q * S + wm * 2 * PW + n16 * 2) * 4;
 
   if (tid < 128) {
     const int c = tid & 63;
@@ -134,16 +143,32 @@ __global__ __launch_bounds__(256, 1) void wino3d_kernel(const Wino3dParams p) {
   const unsigned s_end = (unsigned)((unsigned long long)(lb + 1) * (unsigned)p.total / gridDim.x);
   // the 3 x 16 accumulator tiles are pinned to a[64:255] (wino3d_acc.h); the compiler never sees them
 
-  while (s_cur < s_end) {
-    const int tile_l = __builtin_amdgcn_readfirstlane((int)(s_cur / (unsigned)p.D));
-    const int da = __builtin_amdgcn_readfirstlane((int)(s_cur - (unsigned)tile_l * (unsigned)p.D));
-    const int db = __builtin_amdgcn_readfirstlane((int)min((unsigned)p.D, (unsigned)da + (s_end - s_cur)));
-    s_cur += db - da;
-    const int tw = __builtin_amdgcn_readfirstlane(tile_l % p.tiles_w);
-    const int th = __builtin_amdgcn_readfirstlane((tile_l / p.tiles_w) % p.tiles_h);
-    const int b = __builtin_amdgcn_readfirstlane(tile_l / (p.tiles_w * p.tiles_h));
-    const int h0 = th * C::TH, w0 = tw * C::TWO;
-    const bool wave_live = (h0 + 2 * wm) < p.H;      // (wave-uniform) rows of this wave inside the volume
+  // One segment: the planes da .. db - 1 of tile tile_l.  Instantiated per tile kind (0 ordinary, 1 strip) so that the patch strides stay
+  // immediates; what differs are the lane constants of a tile: the fill's global offsets, the patch address, the output coordinates.
+  auto segment = [&](auto kindc, const int tile_l, const int da, const int db) {
+    constexpr bool STRIP = decltype(kindc)::value == 1;
+    constexpr int PW = STRIP ? C::SPW : C::PW;
+    int b, h0, w0;
+    if constexpr (STRIP) {
+      const int sl = tile_l - p.n_ord;
+      b = __builtin_amdgcn_readfirstlane(sl / p.strips_h);
+      h0 = __builtin_amdgcn_readfirstlane(sl % p.strips_h) * C::STH;
+      w0 = p.tiles_w * C::TWO;
+    } else {
+      const int tw = __builtin_amdgcn_readfirstlane(tile_l % p.tiles_w);
+      const int th = __builtin_amdgcn_readfirstlane((tile_l / p.tiles_w) % p.tiles_h);
+      b = __builtin_amdgcn_readfirstlane(tile_l / (p.tiles_w * p.tiles_h));
+      h0 = th * C::TH; w0 = tw * C::TWO;
+    }
+    int lane_l = lane;
+    asm volatile("" : "+v"(lane_l));                // (per segment: hoisted out of the tile loop the lane constants of both tile kinds would be live in either)
+    const int q = lane_l >> 4, n16 = lane_l & 15;
+    // the lane's 2x2 output tile: row pair rp, column pair cp of the tile (strip: the row pair runs fastest over the lanes, which
+    // keeps the ds_read_b128 lane groups of the patch reads on distinct banks with the 10-wide patch rows)
+    const int rp = STRIP ? 4 * wm + (n16 & 3) : wm, cp = STRIP ? (n16 >> 2) : n16;
+    const bool wave_live = (h0 + 2 * (STRIP ? 4 * wm : wm)) < p.H;      // (wave-uniform) rows of this wave inside the volume
+    // lane-constant part of the patch-read address (floats): cin group q of the chunk, rows 2 rp .., columns 2 cp ..
+    const int lane_lds = (q * S + rp * 2 * PW + cp * 2) * 4;
 
     // per-tile global offsets (bytes inside a plane), 0x80000000 = reads as zero
     unsigned f_off[NFILL];
@@ -254,12 +279,12 @@ __global__ __launch_bounds__(256, 1) void wino3d_kernel(const Wino3dParams p) {
       for (int k = 0; k < 4; ++k) { al_l[k] = epi_tab[c0 + k]; be_l[k] = epi_tab[64 + c0 + k]; }
 #pragma unroll
       for (int pr = 0; pr < 2; ++pr) {
-        const int h = h0 + 2 * wm + pr;
+        const int h = h0 + 2 * rp + pr;
         if (h >= p.H) continue;
         const size_t row_vox = (((size_t)b * p.D + o) * p.H + h) * p.W;
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr) {
-          const int ow = w0 + 2 * n16 + rr;
+          const int ow = w0 + 2 * cp + rr;
           if (ow >= p.W) continue;
           float ov[4];
 #pragma unroll
@@ -400,6 +425,15 @@ __global__ __launch_bounds__(256, 1) void wino3d_kernel(const Wino3dParams p) {
         default: epilogue(std::integral_constant<int, 2>{}, p.D - 1); break;
       }
     }
+  };
+
+  while (s_cur < s_end) {
+    const int tile_l = __builtin_amdgcn_readfirstlane((int)(s_cur / (unsigned)p.D));
+    const int da = __builtin_amdgcn_readfirstlane((int)(s_cur - (unsigned)tile_l * (unsigned)p.D));
+    const int db = __builtin_amdgcn_readfirstlane((int)min((unsigned)p.D, (unsigned)da + (s_end - s_cur)));
+    s_cur += db - da;
+    if (tile_l < p.n_ord) segment(std::integral_constant<int, 0>{}, tile_l, da, db);
+    else segment(std::integral_constant<int, 1>{}, tile_l, da, db);
   }
 }
 
@@ -410,8 +444,17 @@ int launch_wino3d(Wino3dParams& p, hipStream_t st) {
   constexpr int WRITE_AB = MDF_W3_WRITE_AB;   // ab-step of a plane's first chunk at which the NEXT plane goes to LDS (its loads left at the step's start)
   p.tiles_h = (p.H + C::TH - 1) / C::TH;
   p.tiles_w = (p.W + C::TWO - 1) / C::TWO;
-  p.total = (long long)p.B * p.tiles_h * p.tiles_w * p.D;
+  p.strips_h = 0;
+  // a last tile column with 1 .. STW live columns goes to strip tiles: at H = 148 five of them instead of 19 tiles that are three quarters halo
+  const int w_rem = p.W % C::TWO;
+  if (w_rem >= 1 && w_rem <= C::STW && mdf::env_int("MDF_W3_STRIP", 1)) {   // dev A/B and the equality test (read per call): 0 = ordinary tiles only
+    p.tiles_w -= 1;
+    p.strips_h = (p.H + C::STH - 1) / C::STH;
+  }
+  const long long n_ord = (long long)p.B * p.tiles_h * p.tiles_w;
+  p.total = (n_ord + (long long)p.B * p.strips_h) * p.D;
   if (p.total >= (1ll << 31)) return MDF_EUNSUPPORTED;
+  p.n_ord = (int)n_ord;
   constexpr auto kern = &wino3d_kernel<CIN, COUT, NA, WRITE_AB>;
   if (int rc = mdf::ensure_dynamic_lds<kern>(C::LDS_BYTES)) return rc;
   // one block per CU (192 accumulator registers per lane); every block at least ~4 planes so that a segment's two halo planes stay a fraction
