@@ -15,18 +15,20 @@
 // a second kernel sums the slab in a few dozen partial sums per element (no storm of float atomics on the 27*A*B hot addresses).
 //   A operand: lane l holds small[voxel 4j + (l>>4)][a = l&15]      C/D: lane l holds rows 4*(l>>4)..+3, column l&15
 //   B operand: lane l holds big  [voxel 4j + (l>>4)][b = l&15]
+//
+// The 2-D layers of the feature pyramid (net/unit/backbone.py:17-45: Conv2d k3 s1 / k5 s2 / k1, pad (k-1)/2, NHWC) are the same
+// correlation without the depth axis.  ONE body, wgrad_direct_body<KH, KW, MODE3D>, serves both with the z convention of
+// wgrad_lds_body (wgrad_lds.hip) and tests/wgrad_mirror.py: blockIdx.z = kd with the KH = 3 kernel rows resident (3-D), or = kh with
+// one row resident (2-D).  These direct forms run for the shapes the LDS-staged form refuses and behind MDF_WGRAD_LDS=0.
 #include <cstdlib>
 #include "common.h"
+#include "conv_lds_common.h"      // make_rsrc
+#include "wgrad_common.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 typedef unsigned u32;
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);   // raw buffer, dword format (gfx9)
-}
 // One operand element: buffer load at {lane-constant byte offset} + {scalar byte offset}.  No per-load address arithmetic on
 // the VALU (the first version spent 284 VALU instructions per 12 MFMAs on 64-bit addresses, divisions and predicated loads:
 // PMC SQ_INSTS_VALU / SQ_INSTS_MFMA = 23.6); out-of-range offsets (also "negative" ones, which wrap) return 0.
@@ -42,9 +44,9 @@ __device__ __forceinline__ float bload_masked(__amdgpu_buffer_rsrc_t r, u32 lane
 }
 
 struct WgradParams {
-  const float* small_;   // [B,Ds,Hs,Ws,A]
+  const float* small_;   // [B,Ds,Hs,Ws,A]         (2-D: Ds = Db = 1)
   const float* big;      // [B,Db,Hb,Wb,Bc]
-  float* slab;           // [gridDim.x][A][Bc][27]
+  float* slab;           // [gridDim.x][A][Bc][taps]
   int B, Ds, Hs, Ws, Db, Hb, Wb, A, Bc, stride;
   int chunks_per_row;    // ceil(Ws/16)
   long long n_items;     // B*Ds*Hs*chunks_per_row
@@ -54,8 +56,9 @@ struct WgradParams {
   int zero_n;
 };
 
-// the launch also clears the gradient tensor its partial tiles are summed into afterwards (slab_sum_kernel adds with
-// atomics): no separate memset launch per layer
+// the launch also clears the gradient tensor its partial tiles are summed into afterwards (the slab sums add with atomics): no
+// separate memset launch per layer.  (wgrad_lds_body keeps these lines in place, on its VBlock: as a helper they reorder the
+// scalar set-up of every batch instantiation -- profiles/wgrad_refactor.md.)
 __device__ __forceinline__ void zero_slice(float* out, int n) {
   if (!out) return;
   const int nb = gridDim.x * gridDim.y * gridDim.z;
@@ -63,8 +66,10 @@ __device__ __forceinline__ void zero_slice(float* out, int n) {
   for (int i = bid * 256 + threadIdx.x; i < n; i += nb * 256) out[i] = 0.f;
 }
 
-
-__global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
+template <int KH, int KW, bool MODE3D>
+__device__ __forceinline__ void wgrad_direct_body(const WgradParams& p) {
+  constexpr int PAD = (KW - 1) / 2, NT = KH * KW;       // NT tap tiles per wave (3-D: 36 accumulator VGPRs)
+  constexpr int NTAPS = MODE3D ? 3 * NT : KW * KW;
   zero_slice(p.zero_out, p.zero_n);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: the item bookkeeping below runs on the scalar unit
@@ -83,22 +88,24 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
   const __amdgpu_buffer_rsrc_t rb = make_rsrc(p.big, (unsigned)((long long)p.B * p.Db * p.Hb * p.Wb * p.Bc * 4));
   const u32 la = (u32)((q * p.A + ac) * 4), lb = (u32)((q * s * p.Bc + bc) * 4);
 
-  const int kd = blockIdx.z;          // one depth tap per block: 9 accumulator tiles per wave, 3x the independent work
-  f32x4 acc[9];
+  const int z = blockIdx.z;           // one z tap per block: in 3-D 9 accumulator tiles per wave, 3x the independent work
+  f32x4 acc[NT];
 #pragma unroll
-  for (int t = 0; t < 9; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // Software pipeline over the wave's items: the 40 operand loads of item i+1 are in flight while the 36 MFMAs of item i run
+  // Software pipeline over the wave's items: the 4 + 4 NT operand loads of item i+1 are in flight while the 4 NT MFMAs of item i run
   // (the first version loaded, waited and multiplied one kernel row at a time: three exposed memory latencies per item).
-  auto issue = [&](long long item, float (&af)[4], float (&bf)[9][4]) -> int {
+  // issue returns the mask of resident kernel rows whose row of `big` exists (0: the item adds nothing).
+  auto issue = [&](long long item, float (&af)[4], float (&bf)[NT][4]) -> int {
     const unsigned iu = (unsigned)item, r1 = iu / (unsigned)p.chunks_per_row, r2 = r1 / (unsigned)p.Hs;      // (< 2^31 items: 32-bit divisions)
     const int ch = (int)(iu - r1 * (unsigned)p.chunks_per_row), oh = (int)(r1 - r2 * (unsigned)p.Hs);
-    const int n = (int)(r2 / (unsigned)p.Ds), od = (int)(r2 - (unsigned)n * (unsigned)p.Ds);
-    const int id = od * s + kd - 1;
-    if (id < 0 || id >= p.Db) return 0;            // wave-uniform
+    const int n = MODE3D ? (int)(r2 / (unsigned)p.Ds) : (int)r2, od = MODE3D ? (int)(r2 - (unsigned)n * (unsigned)p.Ds) : 0;
+    const int id = MODE3D ? od * s + z - PAD : 0;
+    const int ih0 = MODE3D ? oh * s - PAD : oh * s + z - PAD;        // row of `big` under resident kernel row 0
+    if (MODE3D ? (id < 0 || id >= p.Db) : (ih0 < 0 || ih0 >= p.Hb)) return 0;            // wave-uniform
     const int ow0 = ch * 16;
     const u32 srow = (u32)(((((long long)n * p.Ds + od) * p.Hs + oh) * p.Ws + ow0) * p.A * 4);
-    const bool edge = (ow0 == 0) || ((ow0 + 16) * s + 1 > p.Wb) || (ow0 + 16 > p.Ws);   // wave-uniform
+    const bool edge = (ow0 * s < PAD) || ((ow0 + 16) * s + PAD > p.Wb) || (ow0 + 16 > p.Ws);   // wave-uniform
     if (!edge) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) af[j] = bload(rs, la, srow + (u32)(4 * j * p.A * 4));
@@ -108,46 +115,46 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
     }
     int mask = 0;
 #pragma unroll
-    for (int kh = 0; kh < 3; ++kh) {
-      const int ih = oh * s + kh - 1;
+    for (int kh = 0; kh < KH; ++kh) {
+      const int ih = ih0 + kh;
       if (ih < 0 || ih >= p.Hb) continue;        // wave-uniform
       mask |= 1 << kh;
-      const long long brow = ((((long long)n * p.Db + id) * p.Hb + ih) * p.Wb + (long long)ow0 * s - 1) * p.Bc * 4;   // tap kw = 0 of voxel ow0
+      const long long brow = ((((long long)n * p.Db + id) * p.Hb + ih) * p.Wb + (long long)ow0 * s - PAD) * p.Bc * 4;   // tap kw = 0 of voxel ow0
       if (!edge) {
 #pragma unroll
-        for (int kw = 0; kw < 3; ++kw)
+        for (int kw = 0; kw < KW; ++kw)
 #pragma unroll
-          for (int j = 0; j < 4; ++j) bf[kh * 3 + kw][j] = bload(rb, lb, (u32)(brow + (long long)(4 * j * s + kw) * p.Bc * 4));
+          for (int j = 0; j < 4; ++j) bf[kh * KW + kw][j] = bload(rb, lb, (u32)(brow + (long long)(4 * j * s + kw) * p.Bc * 4));
       } else {
 #pragma unroll
-        for (int kw = 0; kw < 3; ++kw)
+        for (int kw = 0; kw < KW; ++kw)
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             // (the hardware adds lane and scalar offsets WITHOUT wrapping, so a "negative" scalar part is out of range for every
             //  lane: at the row start the offset is formed per lane from the clamped coordinate instead)
-            const int iw = (ow0 + 4 * j + q) * s + kw - 1;
-            const int base = max(ow0 * s - 1, 0);             // first voxel any lane of this chunk can need
-            bf[kh * 3 + kw][j] = bload_masked(rb, (u32)(((max(iw, 0) - base) * p.Bc + bc) * 4),
-                                              (u32)(brow + (long long)(base - (ow0 * s - 1)) * p.Bc * 4), iw >= 0 && iw < p.Wb);
+            const int iw = (ow0 + 4 * j + q) * s + kw - PAD;
+            const int base = max(ow0 * s - PAD, 0);             // first voxel any lane of this chunk can need
+            bf[kh * KW + kw][j] = bload_masked(rb, (u32)(((max(iw, 0) - base) * p.Bc + bc) * 4),
+                                               (u32)(brow + (long long)(base - (ow0 * s - PAD)) * p.Bc * 4), iw >= 0 && iw < p.Wb);
           }
       }
     }
     return mask;
   };
-  auto compute = [&](const float (&af)[4], const float (&bf)[9][4], int mask) {
+  auto compute = [&](const float (&af)[4], const float (&bf)[NT][4], int mask) {
 #pragma unroll
-    for (int kh = 0; kh < 3; ++kh) {
+    for (int kh = 0; kh < KH; ++kh) {
       if (!((mask >> kh) & 1)) continue;         // wave-uniform
 #pragma unroll
-      for (int kw = 0; kw < 3; ++kw)
+      for (int kw = 0; kw < KW; ++kw)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[kh * 3 + kw] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], bf[kh * 3 + kw][j], acc[kh * 3 + kw], 0, 0, 0);
+        for (int j = 0; j < 4; ++j) acc[kh * KW + kw] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], bf[kh * KW + kw][j], acc[kh * KW + kw], 0, 0, 0);
     }
   };
   {
     const long long step = (long long)gridDim.x * p.split;
     long long it = (long long)blockIdx.x * p.split + part;
-    float a0[4], b0[9][4], a1[4], b1[9][4];
+    float a0[4], b0[NT][4], a1[4], b1[NT][4];
     int m0 = (it < p.n_items) ? issue(it, a0, b0) : 0, m1 = 0;
     while (it < p.n_items) {
       const long long nx = it + step;
@@ -160,39 +167,16 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
     }
   }
 
-  // partial tiles of the `split` waves that share a pair: summed through LDS (one 27-KB buffer per pair, the sharing
-  // waves take turns), then one slab write per pair.  Every wave runs the same barrier sequence.
-  __shared__ float red[2][9 * 4 * 64];
-  float* mine = red[(wave / p.split) & 1];
-  for (int turn = 1; turn < p.split; ++turn) {
-    if (part == turn) {
-#pragma unroll
-      for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) mine[(t * 4 + i) * 64 + lane] = acc[t][i];
-    }
-    __syncthreads();
-    if (part == 0) {
-#pragma unroll
-      for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[t][i] += mine[(t * 4 + i) * 64 + lane];
-    }
-    __syncthreads();
-  }
-  if (part == 0 && b_ok) {
-    float* out = p.slab + (long long)blockIdx.x * p.A * p.Bc * 27;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = na * 16 + 4 * q + i;
-      if (row < p.A) {
-        float* o = out + ((long long)row * p.Bc + bcol) * 27 + kd * 9;
-#pragma unroll
-        for (int t = 0; t < 9; ++t) o[t] = acc[t][i];
-      }
-    }
-  }
+  __shared__ float red[2][NT * 4 * 64];       // one buffer per pair (3-D: 27 KB for both)
+  split_wave_sum(acc, red[(wave / p.split) & 1], p.split, part, lane);
+  if (part == 0 && b_ok) store_tap_tiles(acc, p.slab + (long long)blockIdx.x * p.A * p.Bc * NTAPS, na, q, bcol, p.A, p.Bc, NTAPS, z * NT);
 }
+
+__global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) { wgrad_direct_body<3, 3, true>(p); }
+
+template <int KS>
+__global__ __launch_bounds__(256) void wgrad2d_kernel(const WgradParams p) { wgrad_direct_body<1, KS, false>(p); }
+
 
 // ------------------------------------------------------------------------------------------------------------------
 // A = 1 (the `prob` conv, regular.py:43/110): a 1-row `small` would use 1/16 of every MFMA tile.  Re-index the sum by the
@@ -328,127 +312,15 @@ __global__ __launch_bounds__(256) void wgrad_a1_valu_kernel(const WgradParams p)
   }
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// 2-D layers of the feature pyramid (net/unit/backbone.py:17-45: Conv2d k3 s1 / k5 s2, pad (k-1)/2), NHWC:
-//     dw[a][b][kh][kw] = sum over pixels o of  small[o][a] * big[s*o + (kh,kw) - pad][b]
-// Same split-K scheme; blockIdx.z = kernel row kh, a wave keeps the KS tap tiles of that row in registers.
-struct Wgrad2dParams {
-  const float* small_;   // [B,Hs,Ws,A]
-  const float* big;      // [B,Hb,Wb,Bc]
-  float* slab;           // [gridDim.x][A][Bc][KS*KS]
-  int B, Hs, Ws, Hb, Wb, A, Bc, stride;
-  int chunks_per_row;
-  long long n_items;     // B*Hs*chunks_per_row
-  int NB, split;
-  float* zero_out;
-  int zero_n;
-};
-
-template <int KS>
-__global__ __launch_bounds__(256) void wgrad2d_kernel(const Wgrad2dParams p) {
-  zero_slice(p.zero_out, p.zero_n);
-  constexpr int PAD = (KS - 1) / 2;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int q = lane >> 4, c16 = lane & 15;
-  const int pairs_per_block = 4 / p.split;
-  const int pair = blockIdx.y * pairs_per_block + wave / p.split;
-  const int part = wave % p.split;
-  const int na = pair / p.NB, nb = pair % p.NB;
-  const int a = na * 16 + c16, bcol = nb * 16 + c16;
-  const bool b_ok = bcol < p.Bc;
-  const int ac = min(a, p.A - 1), bc = min(bcol, p.Bc - 1);
-  const int kh = blockIdx.z;
-  const int s = p.stride;
-  const __amdgpu_buffer_rsrc_t rs = make_rsrc(p.small_, (unsigned)((long long)p.B * p.Hs * p.Ws * p.A * 4));
-  const __amdgpu_buffer_rsrc_t rb = make_rsrc(p.big, (unsigned)((long long)p.B * p.Hb * p.Wb * p.Bc * 4));
-  const u32 la = (u32)((q * p.A + ac) * 4), lb = (u32)((q * s * p.Bc + bc) * 4);
-  f32x4 acc[KS];
-#pragma unroll
-  for (int t = 0; t < KS; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto issue = [&](long long item, float (&af)[4], float (&bf)[KS][4]) -> int {
-    const unsigned iu = (unsigned)item, r1 = iu / (unsigned)p.chunks_per_row;      // (< 2^31 items: 32-bit divisions)
-    const int ch = (int)(iu - r1 * (unsigned)p.chunks_per_row), n = (int)(r1 / (unsigned)p.Hs), oh = (int)(r1 - (unsigned)n * (unsigned)p.Hs);
-    const int ih = oh * s + kh - PAD;
-    if (ih < 0 || ih >= p.Hb) return 0;            // wave-uniform
-    const int ow0 = ch * 16;
-    const u32 srow = (u32)((((long long)n * p.Hs + oh) * p.Ws + ow0) * p.A * 4);
-    const long long brow = (((long long)n * p.Hb + ih) * p.Wb + (long long)ow0 * s - PAD) * p.Bc * 4;      // tap kw = 0 of voxel ow0
-    const bool edge = (ow0 * s < PAD) || ((ow0 + 16) * s + PAD > p.Wb) || (ow0 + 16 > p.Ws);              // wave-uniform
-    if (!edge) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) af[j] = bload(rs, la, srow + (u32)(4 * j * p.A * 4));
-#pragma unroll
-      for (int kw = 0; kw < KS; ++kw)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bf[kw][j] = bload(rb, lb, (u32)(brow + (long long)(4 * j * s + kw) * p.Bc * 4));
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) af[j] = bload_masked(rs, la, srow + (u32)(4 * j * p.A * 4), ow0 + 4 * j + q < p.Ws);
-#pragma unroll
-      for (int kw = 0; kw < KS; ++kw)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int iw = (ow0 + 4 * j + q) * s + kw - PAD;      // (offsets do not wrap: formed per lane from the clamped coordinate)
-          const int base = max(ow0 * s - PAD, 0);             // first pixel any lane of this chunk can need
-          bf[kw][j] = bload_masked(rb, (u32)(((max(iw, 0) - base) * p.Bc + bc) * 4), (u32)(brow + (long long)(base - (ow0 * s - PAD)) * p.Bc * 4),
-                                   iw >= 0 && iw < p.Wb);
-        }
-    }
-    return 1;
-  };
-  auto compute = [&](const float (&af)[4], const float (&bf)[KS][4], int mask) {
-    if (!mask) return;                             // wave-uniform
-#pragma unroll
-    for (int kw = 0; kw < KS; ++kw)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[kw] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], bf[kw][j], acc[kw], 0, 0, 0);
-  };
-  {   // software pipeline: item i+1's loads in flight under item i's MFMAs
-    const long long step = (long long)gridDim.x * p.split;
-    long long it = (long long)blockIdx.x * p.split + part;
-    float a0[4], b0[KS][4], a1[4], b1[KS][4];
-    int m0 = (it < p.n_items) ? issue(it, a0, b0) : 0, m1 = 0;
-    while (it < p.n_items) {
-      const long long nx = it + step;
-      m1 = (nx < p.n_items) ? issue(nx, a1, b1) : 0;
-      compute(a0, b0, m0);
-      if (nx >= p.n_items) break;
-      it = nx + step;
-      m0 = (it < p.n_items) ? issue(it, a0, b0) : 0;
-      compute(a1, b1, m1);
-    }
+// element i of the sum over slabs ys, ys + gys, ys + 2 gys, ..: two running sums (handed back apart: the callers add them)
+__device__ __forceinline__ void slab_sum_slice(const float* slab, int nslab, int n, int i, int ys, int gys, float& s0, float& s1) {
+  s0 = s1 = 0.f;
+  int k = ys;
+  for (; k + gys < nslab; k += 2 * gys) {
+    s0 += slab[(long long)k * n + i];
+    s1 += slab[(long long)(k + gys) * n + i];
   }
-  __shared__ float red[2][KS * 4 * 64];
-  float* mine = red[(wave / p.split) & 1];
-  for (int turn = 1; turn < p.split; ++turn) {
-    if (part == turn) {
-#pragma unroll
-      for (int t = 0; t < KS; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) mine[(t * 4 + i) * 64 + lane] = acc[t][i];
-    }
-    __syncthreads();
-    if (part == 0) {
-#pragma unroll
-      for (int t = 0; t < KS; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[t][i] += mine[(t * 4 + i) * 64 + lane];
-    }
-    __syncthreads();
-  }
-  if (part == 0 && b_ok) {
-    float* out = p.slab + (long long)blockIdx.x * p.A * p.Bc * (KS * KS);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = na * 16 + 4 * q + i;
-      if (row < p.A) {
-        float* o = out + ((long long)row * p.Bc + bcol) * (KS * KS) + kh * KS;
-#pragma unroll
-        for (int t = 0; t < KS; ++t) o[t] = acc[t][i];
-      }
-    }
-  }
+  if (k < nslab) s0 += slab[(long long)k * n + i];
 }
 
 // out[i] (+)= sum over slabs: blockIdx.y takes every gridDim.y-th slab, partial sums meet in `out` through fp32 atomics
@@ -456,13 +328,8 @@ __global__ __launch_bounds__(256) void wgrad2d_kernel(const Wgrad2dParams p) {
 __global__ void slab_sum_kernel(const float* __restrict__ slab, int nslab, int n, float* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  float s0 = 0.f, s1 = 0.f;
-  int k = blockIdx.y;
-  for (; k + (int)gridDim.y < nslab; k += 2 * gridDim.y) {
-    s0 += slab[(long long)k * n + i];
-    s1 += slab[(long long)(k + gridDim.y) * n + i];
-  }
-  if (k < nslab) s0 += slab[(long long)k * n + i];
+  float s0, s1;
+  slab_sum_slice(slab, nslab, n, i, (int)blockIdx.y, (int)gridDim.y, s0, s1);
   unsafeAtomicAdd(&out[i], s0 + s1);
 }
 
@@ -495,14 +362,112 @@ __global__ void slab_sum_batch_kernel(const SumJobs J) {
   const int i = chunk * 256 + threadIdx.x;
   if (i >= n) return;
   const float* slab = J.slab[j];
-  float s0 = 0.f, s1 = 0.f;
-  int k = ys;
-  for (; k + gys < nslab; k += 2 * gys) {
-    s0 += slab[(long long)k * n + i];
-    s1 += slab[(long long)(k + gys) * n + i];
-  }
-  if (k < nslab) s0 += slab[(long long)k * n + i];
+  float s0, s1;
+  slab_sum_slice(slab, nslab, n, i, ys, gys, s0, s1);
   unsafeAtomicAdd(&J.out[j][i], s0 + s1);
+}
+
+// blocks per launch: every block writes one partial tile set to the slab (PMC: 2 GB written + 2 GB re-read per cfg3 step at
+// 2048 blocks), so no more blocks than it takes to fill the chip a few times over
+int wgrad_target_blocks() { static const int n = mdf::env_pos("MDF_WGRAD_BLOCKS", 1024); return n; }
+// partial-tile bytes per launch (written by the blocks, read again by the sum)
+long long wgrad_slab_cap_bytes() { static const long long n = mdf::env_pos("MDF_WGRAD_SLAB_MIB", 16) << 20; return n; }   // dev A/B
+bool wgrad_use_lds() { static const bool on = mdf::env_flag("MDF_WGRAD_LDS", true); return on; }   // dev A/B
+
+// wgrad_a1_valu_kernel: a thread owns a voxel and four channels; one block per slab, at most one voxel group per block and iteration
+// and two blocks per CU (r03 sweep: 256 / 512 / 1024 / 2048 blocks -> 48 / 25 / 30 / 36 us @8x288x384: the per-block reduction)
+long long a1_valu_blocks(long long voxels, int Bc) {
+  const long long vpb = 256 / (Bc / 4), g = (voxels + vpb - 1) / vpb;
+  return g > 512 ? 512 : g;
+}
+
+// The plan of a layer: the workspace entries size the slabs from it, wgrad_impl and mdf_wgrad_lds_dispatch launch by it.  2-D: Ds = 1.
+mdf::WgradPlan wgrad_plan(bool is3d, int B, int Ds, int Hs, int Ws, int A, int Bc, int ksize) {
+  mdf::WgradPlan pl{};
+  pl.NA = (A + 15) / 16;
+  pl.NB = (Bc + 15) / 16;
+  pl.pairs = pl.NA * pl.NB;
+  pl.split = pl.pairs >= 4 ? 1 : (pl.pairs == 2 ? 2 : 4);
+  pl.gy = (pl.pairs * pl.split + 3) / 4;
+  pl.gz = is3d ? 3 : ksize;
+  pl.n = A * Bc * (is3d ? 27 : ksize * ksize);
+  const long long items = (long long)B * Ds * Hs * ((Ws + 15) / 16);
+  // enough blocks to fill the chip several times over (gz taps x gy pair groups x g), at least `split` chunks each
+  long long g = wgrad_target_blocks() / (pl.gz * pl.gy);
+  if (g > items / pl.split) g = items / pl.split;
+  // every block writes a partial tile set (n floats: 442 KB for 64 x 64 channels in 3-D) that is read again by the sum: <= 16 MiB of
+  // them per launch (r03 sweep, scripts/diag_wgrad_sweep.sh: 64 x 64 @12x18x24 45 -> 37 us, 32 x 32 @24x36x48 50 -> 44 us with
+  // half the blocks; the 16 x 16 layers are not touched by the cap)
+  const long long slab_cap = wgrad_slab_cap_bytes() / ((long long)pl.n * 4);
+  if (g > slab_cap && slab_cap >= 16) g = slab_cap;
+  if (g < 1) g = 1;
+  if (is3d && A == 1 && (Bc == 8 || Bc == 16)) {      // wgrad_a1_valu_kernel: a slab is 216 / 432 floats
+    const long long gv = a1_valu_blocks((long long)B * Ds * Hs * Ws, Bc);
+    if (gv > g) g = gv;
+  }
+  pl.gx = (int)g;
+  return pl;
+}
+
+int sum_slabs(const float* slabs, int nslab, int n, float* dw, hipStream_t st) {
+  hipLaunchKernelGGL(slab_sum_kernel, dim3((n + 255) / 256, mdf::wgrad_sum_slices(nslab)), dim3(256), 0, st, slabs, nslab, n, dw);
+  return mdf::check_launch("slab_sum_kernel");
+}
+
+// 2-D: Ds = 1.  nslab_out set: the partial tiles stay in the workspace for a later mdf_wgrad_sum_batch.
+int wgrad_impl(bool is3d, const float* small_, const float* big, float* dw, float* workspace, int B, int Ds, int Hs, int Ws, int A, int Bc,
+               int ksize, int stride, int accumulate, int* nslab_out, void* stream) {
+  MDF_REQUIRE(small_ && big && dw && workspace, "null pointer argument");
+  MDF_REQUIRE(B > 0 && Ds > 0 && Hs > 0 && Ws > 0, "bad shape");
+  MDF_REQUIRE(stride == 1 || stride == 2, "stride must be 1 or 2");
+  MDF_REQUIRE(is3d || ksize == 1 || ksize == 3 || ksize == 5, "ksize=%d not in {1,3,5}", ksize);
+  MDF_REQUIRE(A >= 1 && A <= 64 && Bc >= 1 && Bc <= 64, "channel counts out of range (A=%d, B=%d)", A, Bc);
+  const int Db = is3d ? Ds * stride : 1;
+  MDF_REQUIRE((long long)B * Ds * Hs * Ws * A * 4 < (1ll << 32) && (long long)B * Db * Hs * Ws * stride * stride * Bc * 4 < (1ll << 32),
+              "operands must fit 32-bit byte offsets");
+  const mdf::WgradPlan pl = wgrad_plan(is3d, B, Ds, Hs, Ws, A, Bc, ksize);
+  WgradParams p{};
+  p.small_ = small_; p.big = big; p.slab = workspace;
+  p.B = B; p.Ds = Ds; p.Hs = Hs; p.Ws = Ws; p.Db = Db; p.Hb = Hs * stride; p.Wb = Ws * stride; p.A = A; p.Bc = Bc; p.stride = stride;
+  p.chunks_per_row = (Ws + 15) / 16;
+  p.n_items = (long long)B * Ds * Hs * p.chunks_per_row;
+  p.NB = pl.NB;
+  p.split = pl.split;
+  p.zero_out = accumulate ? nullptr : dw;
+  p.zero_n = pl.n;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(pl.gx, pl.gy, pl.gz);
+  int gx_used = pl.gx;
+  static const bool a1_valu = mdf::env_flag("MDF_WGRAD_A1_VALU", true);   // dev A/B
+  if (is3d && A == 1 && (Bc == 8 || Bc == 16) && stride == 1 && a1_valu) {
+    const long long voxels = (long long)B * Ds * Hs * Ws, vpb = 256 / (Bc / 4);
+    gx_used = (int)a1_valu_blocks(voxels, Bc);                       // (<= pl.gx: the workspace holds that many slabs)
+    mdf::note_wgrad_plan(3, 0, 1, (int)vpb, (voxels + vpb - 1) / vpb, gx_used, 1, 1, 1);
+    if (Bc == 8) hipLaunchKernelGGL(wgrad_a1_valu_kernel<8>, dim3(gx_used), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(wgrad_a1_valu_kernel<16>, dim3(gx_used), dim3(256), 0, st, p);
+  } else if (is3d && A == 1 && Bc <= 16 && stride == 1) {
+    mdf::note_wgrad_plan(2, 0, 1, 16, p.n_items, pl.gx, 1, 3, 4);
+    hipLaunchKernelGGL(wgrad_a1_kernel, dim3(pl.gx, 1, 3), dim3(256), 0, st, p);
+  } else {
+    int rc_lds = MDF_EUNSUPPORTED;
+    if (wgrad_use_lds()) {
+      rc_lds = mdf_wgrad_lds_dispatch(pl, small_, big, workspace, &gx_used, B, Ds, Hs, Ws, A, Bc, stride, ksize, is3d, p.zero_out, stream);
+      if (rc_lds != MDF_OK && rc_lds != MDF_EUNSUPPORTED) return rc_lds;
+    }
+    if (rc_lds == MDF_EUNSUPPORTED) {
+      gx_used = pl.gx;
+      mdf::note_wgrad_plan(is3d ? 1 : 4, 0, 1, 16, p.n_items, pl.gx, pl.gy, pl.gz, pl.split);
+      if (is3d) hipLaunchKernelGGL(wgrad_kernel, grid, dim3(256), 0, st, p);
+      else if (ksize == 1) hipLaunchKernelGGL(wgrad2d_kernel<1>, grid, dim3(256), 0, st, p);
+      else if (ksize == 3) hipLaunchKernelGGL(wgrad2d_kernel<3>, grid, dim3(256), 0, st, p);
+      else hipLaunchKernelGGL(wgrad2d_kernel<5>, grid, dim3(256), 0, st, p);
+      if (!is3d) if (int rc = mdf::check_launch("wgrad2d_kernel")) return rc;
+    }
+  }
+  // (mdf_last_launch: a 3-D entry names wgrad_kernel whichever form ran; a 2-D entry names the LDS form itself)
+  if (is3d) if (int rc = mdf::check_launch("wgrad_kernel")) return rc;
+  if (nslab_out) { *nslab_out = gx_used; return MDF_OK; }      // the caller sums the partial tiles later (mdf_wgrad_sum_batch)
+  return sum_slabs(workspace, gx_used, pl.n, dw, st);
 }
 
 }  // namespace
@@ -518,12 +483,9 @@ extern "C" int mdf_wgrad_sum_batch(const float* const* slabs, float* const* outs
       const int g = first + j;
       MDF_REQUIRE(slabs[g] && outs[g] && nslabs[g] >= 1 && ns[g] >= 1, "job %d: bad slab / out / counts", g);
       J.slab[j] = slabs[g]; J.out[j] = outs[g]; J.nslab[j] = nslabs[g]; J.n[j] = ns[g];
-      int gys = nslabs[g] / 8;                  // >= 8 slabs per partial sum
-      if (gys < 1) gys = 1;
-      if (gys > 32) gys = 32;
-      J.gys[j] = gys;
+      J.gys[j] = mdf::wgrad_sum_slices(nslabs[g]);
       J.blk0[j] = blk;
-      blk += ((ns[g] + 255) / 256) * gys;
+      blk += ((ns[g] + 255) / 256) * J.gys[j];
     }
     J.blk0[J.njobs] = blk;
     hipLaunchKernelGGL(slab_sum_batch_kernel, dim3(blk), dim3(256), 0, (hipStream_t)stream, J);
@@ -532,182 +494,38 @@ extern "C" int mdf_wgrad_sum_batch(const float* const* slabs, float* const* outs
   return MDF_OK;
 }
 
-int mdf_wgrad_lds_dispatch(const float* small_, const float* big, float* workspace, int* gx_io, int B, int Ds, int Hs, int Ws, int A, int Bc,
-                           int stride, int ksize, int is3d, float* zero_out, int zero_n, void* stream);
-// blocks per launch: every block writes one partial tile set to the slab (PMC: 2 GB written + 2 GB re-read per cfg3 step at
-// 2048 blocks), so no more blocks than it takes to fill the chip a few times over
-static int wgrad_target_blocks() { static const int n = mdf::env_pos("MDF_WGRAD_BLOCKS", 1024); return n; }
-// partial-tile bytes per launch (written by the blocks, read again by the sum)
-static long long wgrad_slab_cap_bytes() { static const long long n = mdf::env_pos("MDF_WGRAD_SLAB_MIB", 16) << 20; return n; }   // dev A/B
-static bool wgrad_use_lds() { static const bool on = mdf::env_flag("MDF_WGRAD_LDS", true); return on; }   // dev A/B
-
 extern "C" int64_t mdf_conv3d_wgrad_workspace(int B, int Ds, int Hs, int Ws, int A, int Bc) {
   if (B < 1 || Ds < 1 || Hs < 1 || Ws < 1 || A < 1 || Bc < 1) return 0;
-  const long long items = (long long)B * Ds * Hs * ((Ws + 15) / 16);
-  const int pairs = ((A + 15) / 16) * ((Bc + 15) / 16);
-  const int split = pairs >= 4 ? 1 : (pairs == 2 ? 2 : 4);
-  const int gy = (pairs * split + 3) / 4;
-  // enough blocks to fill the chip several times over (3 depth taps x gy pair groups x g), at least `split` chunks each
-  long long g = wgrad_target_blocks() / (3 * gy);
-  if (g > items / split) g = items / split;
-  // every block writes a partial tile set (A*Bc*27 floats: 442 KB for 64 x 64 channels) that is read again by the sum: <= 16 MiB of
-  // them per launch (r03 sweep, scripts/diag_wgrad_sweep.sh: 64 x 64 @12x18x24 45 -> 37 us, 32 x 32 @24x36x48 50 -> 44 us with
-  // half the blocks; the 16 x 16 layers are not touched by the cap)
-  const long long slab_cap = wgrad_slab_cap_bytes() / ((long long)A * Bc * 27 * 4);
-  if (g > slab_cap && slab_cap >= 16) g = slab_cap;
-  if (g < 1) g = 1;
-  if (A == 1 && (Bc == 8 || Bc == 16)) {      // wgrad_a1_valu_kernel: one block per slab, a slab is 216 / 432 floats
-    const long long vpb = 256 / (Bc / 4);
-    long long gv = ((long long)B * Ds * Hs * Ws + vpb - 1) / vpb;
-    if (gv > 512) gv = 512;
-    if (gv > g) g = gv;
-  }
-  return g * A * Bc * 27;   // floats
-}
-
-static int conv3d_wgrad_impl(const float* small_, const float* big, float* dw, float* workspace, int B, int Ds, int Hs, int Ws,
-                             int A, int Bc, int stride, int accumulate, int* nslab_out, void* stream) {
-  MDF_REQUIRE(small_ && big && dw && workspace, "null pointer argument");
-  MDF_REQUIRE(B > 0 && Ds > 0 && Hs > 0 && Ws > 0, "bad shape");
-  MDF_REQUIRE(stride == 1 || stride == 2, "stride must be 1 or 2");
-  MDF_REQUIRE(A >= 1 && A <= 64 && Bc >= 1 && Bc <= 64, "channel counts out of range (A=%d, B=%d)", A, Bc);
-  MDF_REQUIRE((long long)B * Ds * Hs * Ws * A * 4 < (1ll << 32) && (long long)B * Ds * Hs * Ws * stride * stride * stride * Bc * 4 < (1ll << 32),
-              "operand volumes must fit 32-bit byte offsets");
-  WgradParams p{};
-  p.small_ = small_; p.big = big; p.slab = workspace;
-  p.B = B; p.Ds = Ds; p.Hs = Hs; p.Ws = Ws; p.Db = Ds * stride; p.Hb = Hs * stride; p.Wb = Ws * stride; p.A = A; p.Bc = Bc; p.stride = stride;
-  p.chunks_per_row = (Ws + 15) / 16;
-  p.n_items = (long long)B * Ds * Hs * p.chunks_per_row;
-  const int NA = (A + 15) / 16;
-  p.NB = (Bc + 15) / 16;
-  const int pairs = NA * p.NB;
-  p.split = pairs >= 4 ? 1 : (pairs == 2 ? 2 : 4);
-  const int gy = (pairs * p.split + 3) / 4;
-  const int gx = (int)(mdf_conv3d_wgrad_workspace(B, Ds, Hs, Ws, A, Bc) / ((long long)A * Bc * 27));
-  const int n = A * Bc * 27;
-  p.zero_out = accumulate ? nullptr : dw;
-  p.zero_n = n;
-  int gx_used = gx;
-  int rc_lds = MDF_EUNSUPPORTED;
-  static const bool a1_valu = mdf::env_flag("MDF_WGRAD_A1_VALU", true);   // dev A/B
-  if (A == 1 && (Bc == 8 || Bc == 16) && stride == 1 && a1_valu) {
-    const long long vpb = 256 / (Bc / 4);
-    long long g = ((long long)B * Ds * Hs * Ws + vpb - 1) / vpb;     // at most one voxel group per block and iteration ...
-    if (g > 512) g = 512;                                            // ... and two blocks per CU (r03 sweep: 256 / 512 / 1024 / 2048 blocks -> 48 / 25 / 30 / 36 us @8x288x384: the per-block reduction)
-    if (g > gx) g = gx;                                              // (the workspace holds gx slabs)
-    gx_used = (int)g;
-    mdf::note_wgrad_plan(3, 0, 1, (int)vpb, ((long long)B * Ds * Hs * Ws + vpb - 1) / vpb, gx_used, 1, 1, 1);
-    if (Bc == 8) hipLaunchKernelGGL(wgrad_a1_valu_kernel<8>, dim3(gx_used), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(wgrad_a1_valu_kernel<16>, dim3(gx_used), dim3(256), 0, (hipStream_t)stream, p);
-  } else if (A == 1 && Bc <= 16 && stride == 1) {
-    mdf::note_wgrad_plan(2, 0, 1, 16, p.n_items, gx, 1, 3, 4);
-    hipLaunchKernelGGL(wgrad_a1_kernel, dim3(gx, 1, 3), dim3(256), 0, (hipStream_t)stream, p);
-  } else {
-    if (wgrad_use_lds()) {
-      gx_used = gx;
-      rc_lds = mdf_wgrad_lds_dispatch(small_, big, workspace, &gx_used, B, Ds, Hs, Ws, A, Bc, stride, 3, 1, p.zero_out, n, stream);
-      if (rc_lds != MDF_OK && rc_lds != MDF_EUNSUPPORTED) return rc_lds;
-    }
-    if (rc_lds == MDF_EUNSUPPORTED) {
-      gx_used = gx;
-      mdf::note_wgrad_plan(1, 0, 1, 16, p.n_items, gx, gy, 3, p.split);
-      hipLaunchKernelGGL(wgrad_kernel, dim3(gx, gy, 3), dim3(256), 0, (hipStream_t)stream, p);
-    }
-  }
-  if (int rc = mdf::check_launch("wgrad_kernel")) return rc;
-  if (nslab_out) { *nslab_out = gx_used; return MDF_OK; }      // the caller sums the partial tiles later (mdf_wgrad_sum_batch)
-  int gys = gx_used / 8;                  // >= 8 slabs per partial sum
-  if (gys < 1) gys = 1;
-  if (gys > 32) gys = 32;
-  hipLaunchKernelGGL(slab_sum_kernel, dim3((n + 255) / 256, gys), dim3(256), 0, (hipStream_t)stream, workspace, gx_used, n, dw);
-  return mdf::check_launch("slab_sum_kernel");
-}
-
-extern "C" int mdf_conv3d_wgrad(const float* small_, const float* big, float* dw, float* workspace, int B, int Ds, int Hs, int Ws,
-                                int A, int Bc, int stride, int accumulate, void* stream) {
-  return conv3d_wgrad_impl(small_, big, dw, workspace, B, Ds, Hs, Ws, A, Bc, stride, accumulate, nullptr, stream);
-}
-
-// The same without the final sum: dw is cleared, the partial tiles stay in `workspace` as *nslab_out slabs of A*Bc*27 floats
-// ([A][Bc][27] each) for a later mdf_wgrad_sum_batch (one launch for all the layers of a backward pass).
-extern "C" int mdf_conv3d_wgrad_partial(const float* small_, const float* big, float* dw, float* workspace, int B, int Ds, int Hs, int Ws,
-                                        int A, int Bc, int stride, int* nslab_out, void* stream) {
-  MDF_REQUIRE(nslab_out, "nslab_out is null");
-  return conv3d_wgrad_impl(small_, big, dw, workspace, B, Ds, Hs, Ws, A, Bc, stride, 0, nslab_out, stream);
-}
-
-static long long wgrad2d_grid(int B, int Hs, int Ws, int A, int Bc, int ksize, int* split_out, int* gy_out) {
-  const long long items = (long long)B * Hs * ((Ws + 15) / 16);
-  const int pairs = ((A + 15) / 16) * ((Bc + 15) / 16);
-  const int split = pairs >= 4 ? 1 : (pairs == 2 ? 2 : 4);
-  const int gy = (pairs * split + 3) / 4;
-  long long g = wgrad_target_blocks() / (ksize * gy);
-  if (g > items / split) g = items / split;
-  const long long slab_cap = wgrad_slab_cap_bytes() / ((long long)A * Bc * ksize * ksize * 4);
-  if (g > slab_cap && slab_cap >= 16) g = slab_cap;
-  if (g < 1) g = 1;
-  if (split_out) *split_out = split;
-  if (gy_out) *gy_out = gy;
-  return g;
+  const mdf::WgradPlan pl = wgrad_plan(true, B, Ds, Hs, Ws, A, Bc, 3);
+  return (int64_t)pl.gx * pl.n;   // floats
 }
 
 extern "C" int64_t mdf_conv2d_wgrad_workspace(int B, int Hs, int Ws, int A, int Bc, int ksize) {
   if (B < 1 || Hs < 1 || Ws < 1 || A < 1 || Bc < 1 || ksize < 1) return 0;
-  return wgrad2d_grid(B, Hs, Ws, A, Bc, ksize, nullptr, nullptr) * A * Bc * ksize * ksize;
+  const mdf::WgradPlan pl = wgrad_plan(false, B, 1, Hs, Ws, A, Bc, ksize);
+  return (int64_t)pl.gx * pl.n;
 }
 
-static int conv2d_wgrad_impl(const float* small_, const float* big, float* dw, float* workspace, int B, int Hs, int Ws, int A, int Bc,
-                             int ksize, int stride, int accumulate, int* nslab_out, void* stream) {
-  MDF_REQUIRE(small_ && big && dw && workspace, "null pointer argument");
-  MDF_REQUIRE(B > 0 && Hs > 0 && Ws > 0, "bad shape");
-  MDF_REQUIRE(stride == 1 || stride == 2, "stride must be 1 or 2");
-  MDF_REQUIRE(ksize == 1 || ksize == 3 || ksize == 5, "ksize=%d not in {1,3,5}", ksize);
-  MDF_REQUIRE(A >= 1 && A <= 64 && Bc >= 1 && Bc <= 64, "channel counts out of range (A=%d, B=%d)", A, Bc);
-  MDF_REQUIRE((long long)B * Hs * Ws * A * 4 < (1ll << 32) && (long long)B * Hs * Ws * stride * stride * Bc * 4 < (1ll << 32),
-              "operand maps must fit 32-bit byte offsets");
-  Wgrad2dParams p{};
-  p.small_ = small_; p.big = big; p.slab = workspace;
-  p.B = B; p.Hs = Hs; p.Ws = Ws; p.Hb = Hs * stride; p.Wb = Ws * stride; p.A = A; p.Bc = Bc; p.stride = stride;
-  p.chunks_per_row = (Ws + 15) / 16;
-  p.n_items = (long long)B * Hs * p.chunks_per_row;
-  p.NB = (Bc + 15) / 16;
-  int gy = 1;
-  const int gx = (int)wgrad2d_grid(B, Hs, Ws, A, Bc, ksize, &p.split, &gy);
-  const dim3 grid(gx, gy, ksize);
-  hipStream_t st = (hipStream_t)stream;
-  const int n = A * Bc * ksize * ksize;
-  p.zero_out = accumulate ? nullptr : dw;
-  p.zero_n = n;
-  int gx_used = gx, rc_lds = MDF_EUNSUPPORTED;
-  if (wgrad_use_lds()) {
-    gx_used = gx;
-    rc_lds = mdf_wgrad_lds_dispatch(small_, big, workspace, &gx_used, B, 1, Hs, Ws, A, Bc, stride, ksize, 0, p.zero_out, n, stream);
-    if (rc_lds != MDF_OK && rc_lds != MDF_EUNSUPPORTED) return rc_lds;
-  }
-  if (rc_lds == MDF_EUNSUPPORTED) {
-    gx_used = gx;
-    mdf::note_wgrad_plan(4, 0, 1, 16, p.n_items, gx, gy, ksize, p.split);
-    if (ksize == 1) hipLaunchKernelGGL(wgrad2d_kernel<1>, grid, dim3(256), 0, st, p);
-    else if (ksize == 3) hipLaunchKernelGGL(wgrad2d_kernel<3>, grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(wgrad2d_kernel<5>, grid, dim3(256), 0, st, p);
-    if (int rc = mdf::check_launch("wgrad2d_kernel")) return rc;
-  }
-  if (nslab_out) { *nslab_out = gx_used; return MDF_OK; }
-  int gys = gx_used / 8;
-  if (gys < 1) gys = 1;
-  if (gys > 32) gys = 32;
-  hipLaunchKernelGGL(slab_sum_kernel, dim3((n + 255) / 256, gys), dim3(256), 0, st, workspace, gx_used, n, dw);
-  return mdf::check_launch("slab_sum_kernel");
+extern "C" int mdf_conv3d_wgrad(const float* small_, const float* big, float* dw, float* workspace, int B, int Ds, int Hs, int Ws,
+                                int A, int Bc, int stride, int accumulate, void* stream) {
+  return wgrad_impl(true, small_, big, dw, workspace, B, Ds, Hs, Ws, A, Bc, 3, stride, accumulate, nullptr, stream);
+}
+
+// The same without the final sum: dw is cleared, the partial tiles stay in `workspace` as *nslab_out slabs of dw.numel() floats
+// ([A][Bc][taps] each) for a later mdf_wgrad_sum_batch (one launch for all the layers of a backward pass).
+extern "C" int mdf_conv3d_wgrad_partial(const float* small_, const float* big, float* dw, float* workspace, int B, int Ds, int Hs, int Ws,
+                                        int A, int Bc, int stride, int* nslab_out, void* stream) {
+  MDF_REQUIRE(nslab_out, "nslab_out is null");
+  return wgrad_impl(true, small_, big, dw, workspace, B, Ds, Hs, Ws, A, Bc, 3, stride, 0, nslab_out, stream);
 }
 
 extern "C" int mdf_conv2d_wgrad(const float* small_, const float* big, float* dw, float* workspace, int B, int Hs, int Ws, int A, int Bc,
                                 int ksize, int stride, int accumulate, void* stream) {
-  return conv2d_wgrad_impl(small_, big, dw, workspace, B, Hs, Ws, A, Bc, ksize, stride, accumulate, nullptr, stream);
+  return wgrad_impl(false, small_, big, dw, workspace, B, 1, Hs, Ws, A, Bc, ksize, stride, accumulate, nullptr, stream);
 }
 
 extern "C" int mdf_conv2d_wgrad_partial(const float* small_, const float* big, float* dw, float* workspace, int B, int Hs, int Ws, int A, int Bc,
                                         int ksize, int stride, int* nslab_out, void* stream) {
   MDF_REQUIRE(nslab_out, "nslab_out is null");
-  return conv2d_wgrad_impl(small_, big, dw, workspace, B, Hs, Ws, A, Bc, ksize, stride, 0, nslab_out, stream);
+  return wgrad_impl(false, small_, big, dw, workspace, B, 1, Hs, Ws, A, Bc, ksize, stride, 0, nslab_out, stream);
 }
-

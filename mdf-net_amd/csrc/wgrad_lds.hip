@@ -9,13 +9,16 @@
 // 64-lane read).  Voxel strides in LDS are padded so that the two 16-lane groups of a 32-lane half hit disjoint banks.
 //
 //     dw[a][b][z][kh][kw] (+)= sum_o small[o][a] * big[s*o + tap - pad][b]       z = blockIdx.z (kd in 3-D, kh in 2-D)
+//
+// Layout of the file: wgrad_lds_body (one body for every form), its one-layer and job-table kernels, THE list of instantiations
+// (WgInsts: both launch paths visit it), the deferred-launch entries, and mdf_wgrad_lds_dispatch, which takes the layer's WgradPlan
+// from wgrad.hip (wgrad_common.h) and adds the tile search.  The split-wave sum and the unpacked tile store are wgrad_common.h's.
 #include <cstdlib>
 #include <vector>
 #include "common.h"
+#include "wgrad_common.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct WgradLdsParams {
   const float* small_;   // rows of Ws voxels x A channels
@@ -207,35 +210,11 @@ __device__ __forceinline__ void wgrad_lds_body(const WgradLdsParams& p, const VB
   }
 
   // partial tiles of the `split` waves that share a pair: summed through LDS (the staging area is free now)
-  float* mine = lds + (wave / p.split) * (KH * NT * 4 * 64);
-  for (int turn = 1; turn < p.split; ++turn) {
-    if (part == turn) {
-#pragma unroll
-      for (int t = 0; t < KH * NT; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) mine[(t * 4 + i) * 64 + lane] = acc[t][i];
-    }
-    __syncthreads();
-    if (part == 0) {
-#pragma unroll
-      for (int t = 0; t < KH * NT; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[t][i] += mine[(t * 4 + i) * 64 + lane];
-    }
-    __syncthreads();
-  }
+  split_wave_sum(acc, lds + (wave / p.split) * (KH * NT * 4 * 64), p.split, part, lane);
   if (part == 0 && b_ok) {
     float* out = p.slab + (long long)vb.bx * p.A * p.Bc * p.ntaps_total;
     if constexpr (R == 0) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = na * 16 + 4 * q + i;
-        if (row < p.A) {
-          float* o = out + ((long long)row * p.Bc + bcol) * p.ntaps_total + z * (KH * KW);
-#pragma unroll
-          for (int t = 0; t < KH * KW; ++t) o[t] = acc[t][i];
-        }
-      }
+      store_tap_tiles(acc, out, na, q, bcol, p.A, p.Bc, p.ntaps_total, z * (KH * KW));
     } else {
       // tile (row, column) = ((sa, a), (sb, b)); chain ts holds tap kw = ts*TSTEP + sa + sb.  Every (a, b, kw) is stored once: by the
       // block with the largest row shift that reaches it (sa = min(m, pa-1), m = kw - ts*TSTEP).
@@ -318,37 +297,45 @@ int padded_stride(int C, int step) {
   return C + 4;
 }
 
+// ---- THE list of instantiations.  A form is (KH, KW, MODE3D, R); TH = 2 and 4 exist in 3-D only: the tile search below gives a 2-D
+// layer one-row tiles (TH = 4 is reached with MDF_WGRAD_TH=4).  Each entry is built as the one-layer and as the batch kernel.
+struct WgKey {
+  int kh, kw;
+  bool m3;
+  int r, th;
+  constexpr bool operator==(const WgKey& o) const { return kh == o.kh && kw == o.kw && m3 == o.m3 && r == o.r && th == o.th; }
+};
+template <int KH, int KW, bool M3, int R, int TH>
+struct WgInst {
+  static constexpr WgKey key{KH, KW, M3, R, TH};
+  static constexpr auto single = &wgrad_lds_kernel<KH, KW, M3, R, TH>;
+  static constexpr auto batch = &wgrad_lds_batch_kernel<KH, KW, M3, R, TH>;
+};
+template <class... I> struct WgList {};
+using WgInsts = WgList<WgInst<3, 3, true, 2, 1>, WgInst<3, 3, true, 2, 2>, WgInst<3, 3, true, 2, 4>,
+                       WgInst<3, 3, true, 1, 1>, WgInst<3, 3, true, 1, 2>, WgInst<3, 3, true, 1, 4>,
+                       WgInst<3, 3, true, 0, 1>, WgInst<3, 3, true, 0, 2>, WgInst<3, 3, true, 0, 4>,
+                       WgInst<1, 3, false, 2, 1>, WgInst<1, 3, false, 1, 1>, WgInst<1, 3, false, 0, 1>,
+                       WgInst<1, 5, false, 0, 1>, WgInst<1, 1, false, 0, 1>>;
+// f(the entry with this key); MDF_EUNSUPPORTED when the list has none
+template <class F, class... I>
+int visit_inst(const WgKey& key, F&& f, WgList<I...>) {
+  int rc = MDF_EUNSUPPORTED;
+  (void)((I::key == key ? (rc = f(I{}), true) : false) || ...);
+  return rc;
+}
+// (the attribute asks for the family's ceiling of 150 KB, not the launch's own size: it is set once per kernel and device)
+template <auto KERN, class Arg>
+int launch_lds(dim3 grid, size_t lds, hipStream_t st, const Arg& arg, const char* name) {
+  if (int rc = mdf::ensure_dynamic_lds<KERN>(150 * 1024)) return rc;
+  hipLaunchKernelGGL(KERN, grid, dim3(256), lds, st, arg);
+  return mdf::check_launch(name);
+}
+
 // ---- deferred launches (mdf_wgrad_batch_begin / _flush): the calling thread's dispatches are recorded instead of launched
-struct PendingJob { int key; WgradLdsParams p; int gx, gy, gz; size_t lds; };
+struct PendingJob { WgKey key; WgradLdsParams p; int gx, gy, gz; size_t lds; };
 thread_local bool g_batching = false;
 thread_local std::vector<PendingJob>* g_pending = nullptr;
-
-template <int KH, int KW, bool MODE3D, int R, int TH>
-int launch_batch(const WgradBatch& tb, int blocks, size_t lds, hipStream_t st) {
-  static bool attr_done[64] = {};
-  int dev_id = 0;
-  (void)hipGetDevice(&dev_id);
-  if (dev_id < 0 || dev_id >= 64 || !attr_done[dev_id]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_lds_batch_kernel<KH, KW, MODE3D, R, TH>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    if (e != hipSuccess) return mdf::fail(MDF_EHIP, "hipFuncSetAttribute(dynamic LDS): %s", hipGetErrorString(e));
-    if (dev_id >= 0 && dev_id < 64) attr_done[dev_id] = true;
-  }
-  hipLaunchKernelGGL((wgrad_lds_batch_kernel<KH, KW, MODE3D, R, TH>), dim3(blocks), dim3(256), lds, st, tb);
-  return mdf::check_launch("wgrad_lds_batch_kernel");
-}
-
-// key = ((KH * 8 + KW) * 2 + MODE3D) * 4 + R) * 8 + TH
-constexpr int wg_key(int kh, int kw, bool m3, int r, int th) { return ((((kh * 8 + kw) * 2 + (m3 ? 1 : 0)) * 4 + r) * 8) + th; }
-
-int launch_batch_key(int key, const WgradBatch& tb, int blocks, size_t lds, hipStream_t st) {
-#define WGB(KHv, KWv, M3, Rv, THv) if (key == wg_key(KHv, KWv, M3, Rv, THv)) return launch_batch<KHv, KWv, M3, Rv, THv>(tb, blocks, lds, st);
-#define WGB3(KHv, KWv, M3, Rv) WGB(KHv, KWv, M3, Rv, 1) WGB(KHv, KWv, M3, Rv, 2) WGB(KHv, KWv, M3, Rv, 4)
-  WGB3(3, 3, true, 2) WGB3(3, 3, true, 1) WGB3(3, 3, true, 0) WGB3(1, 3, false, 2) WGB3(1, 3, false, 1) WGB3(1, 3, false, 0) WGB3(1, 5, false, 0) WGB3(1, 1, false, 0)
-#undef WGB3
-#undef WGB
-  return mdf::fail(MDF_EUNSUPPORTED, "wgrad batch: no kernel for key %d", key);
-}
 
 }  // namespace
 
@@ -372,7 +359,7 @@ extern "C" int mdf_wgrad_batch_flush(void* stream) {
     int blocks = 0;
     size_t lds = 0;
     for (size_t k = i; k < jobs.size() && tb.njobs < kWgradBatchMax; ++k) {
-      if (done[k] || jobs[k].key != jobs[i].key) continue;
+      if (done[k] || !(jobs[k].key == jobs[i].key)) continue;
       const PendingJob& jb = jobs[k];
       tb.first[tb.njobs] = blocks;
       tb.gx[tb.njobs] = jb.gx; tb.gy[tb.njobs] = jb.gy;
@@ -383,29 +370,27 @@ extern "C" int mdf_wgrad_batch_flush(void* stream) {
       done[k] = 1;
     }
     tb.first[tb.njobs] = blocks;
-    if (int rc = launch_batch_key(jobs[i].key, tb, blocks, lds, (hipStream_t)stream)) return rc;
+    if (int rc = visit_inst(jobs[i].key, [&](auto inst) {
+          return launch_lds<decltype(inst)::batch>(dim3(blocks), lds, (hipStream_t)stream, tb, "wgrad_lds_batch_kernel");
+        }, WgInsts{}))
+      return rc;      // (only listed instantiations are recorded)
   }
   return MDF_OK;
 }
 
-// returns MDF_EUNSUPPORTED when the shape has no LDS instantiation (the caller falls back to the direct kernels)
-int mdf_wgrad_lds_dispatch(const float* small_, const float* big, float* workspace, int* gx_io, int B, int Ds, int Hs, int Ws, int A, int Bc,
-                           int stride, int ksize, int is3d, float* zero_out, int zero_n, void* stream) {
+int mdf_wgrad_lds_dispatch(const mdf::WgradPlan& pl, const float* small_, const float* big, float* workspace, int* gx_io, int B, int Ds, int Hs,
+                           int Ws, int A, int Bc, int stride, int ksize, int is3d, float* zero_out, void* stream) {
   if ((A & 3) || (Bc & 3)) return MDF_EUNSUPPORTED;
   WgradLdsParams p{};
-  p.small_ = small_; p.big = big; p.slab = workspace; p.zero_out = zero_out; p.zero_n = zero_n;
-  p.B = B; p.Ds = Ds; p.Hs = Hs; p.Ws = Ws; p.Db = Ds * stride; p.Hb = Hs * stride; p.Wb = Ws * stride; p.A = A; p.Bc = Bc; p.stride = stride;
-  if (!is3d) { p.Ds = 1; p.Db = 1; }
+  p.small_ = small_; p.big = big; p.slab = workspace; p.zero_out = zero_out; p.zero_n = pl.n;
+  p.B = B; p.Ds = Ds; p.Hs = Hs; p.Ws = Ws; p.Db = is3d ? Ds * stride : 1; p.Hb = Hs * stride; p.Wb = Ws * stride; p.A = A; p.Bc = Bc; p.stride = stride;
   p.pad = (ksize - 1) / 2;
   p.AS = padded_stride(A, 1);
   p.BS = padded_stride(Bc, stride);
-  const int NA = (A + 15) / 16;
-  p.NB = (Bc + 15) / 16;
-  const int pairs = NA * p.NB;
-  p.split = pairs >= 4 ? 1 : (pairs == 2 ? 2 : 4);
-  const int gy = (pairs * p.split + 3) / 4;
+  p.NB = pl.NB;
+  p.split = pl.split;
   const int KH = is3d ? 3 : 1, KW = ksize;
-  p.ntaps_total = is3d ? 27 : ksize * ksize;
+  p.ntaps_total = pl.n / (A * Bc);
   // tap packing for the few-channel layers (see the kernel): shifts of `small` in the rows, of `big` in the columns
   static const bool pack_on = mdf::env_flag("MDF_WGRAD_PACK", true);   // dev A/B
   p.pa = p.pb = 1;
@@ -444,6 +429,7 @@ int mdf_wgrad_lds_dispatch(const float* small_, const float* big, float* workspa
   if (best_tv == 0) return MDF_EUNSUPPORTED;
   p.tv = best_tv;
   const int TH = best_th;
+  MDF_REQUIRE(is3d || TH == 1, "a 2-D weight gradient has one-row tiles (TH=%d): no other instantiation is built", TH);
   p.wtiles = (Ws + hal + p.tv - 1) / p.tv;      // (packed rows sum over v - sa: the tiles reach pa-1 voxels past the row)
   p.htiles = (Hs + TH - 1) / TH;
   p.n_tiles = (long long)B * p.Ds * p.htiles * p.wtiles;
@@ -451,47 +437,19 @@ int mdf_wgrad_lds_dispatch(const float* small_, const float* big, float* workspa
   const size_t red = (size_t)2 * KH * KW * 4 * 64 * sizeof(float);
   if (lds < red) lds = red;
   if (lds > 150 * 1024) return MDF_EUNSUPPORTED;
-  int gx = *gx_io;                               // in: slabs the workspace holds; out: blocks launched (= slabs written)
+  int gx = *gx_io;
   if (gx > p.n_tiles) gx = (int)p.n_tiles;
   if (gx > p.n_tiles / 2 && p.n_tiles / 2 >= 64) gx = (int)(p.n_tiles / 2);     // >= 2 tiles per block: the second tile's loads fly during the first one's MFMAs
   if (gx < 1) gx = 1;
-  *gx_io = gx;
-  const dim3 grid(gx, gy, is3d ? 3 : ksize);
-  hipStream_t st = (hipStream_t)stream;
-  mdf::note_wgrad_plan(0, R, TH, p.tv, p.n_tiles, gx, gy, (int)grid.z, p.split);      // (a shape without an instantiation falls back: the direct form overwrites it)
-#define WG_LAUNCH_TH(KHv, KWv, M3, Rv, THv)                                                                               \
-  {                                                                                                                        \
-    if (g_batching) {       /* recorded: launched by mdf_wgrad_batch_flush together with the other layers of this instantiation */ \
-      g_pending->push_back(PendingJob{wg_key(KHv, KWv, M3, Rv, THv), p, (int)grid.x, (int)grid.y, (int)grid.z, lds});       \
-      return MDF_OK;                                                                                                       \
-    }                                                                                                                      \
-    static bool attr_done[64] = {};                                                                                        \
-    int dev_id = 0;                                                                                                        \
-    (void)hipGetDevice(&dev_id);                                                                                           \
-    if (dev_id < 0 || dev_id >= 64 || !attr_done[dev_id]) {                                                                \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_lds_kernel<KHv, KWv, M3, Rv, THv>),          \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);                          \
-      if (e != hipSuccess) return mdf::fail(MDF_EHIP, "hipFuncSetAttribute(dynamic LDS): %s", hipGetErrorString(e));       \
-      if (dev_id >= 0 && dev_id < 64) attr_done[dev_id] = true;                                                            \
-    }                                                                                                                      \
-    hipLaunchKernelGGL((wgrad_lds_kernel<KHv, KWv, M3, Rv, THv>), grid, dim3(256), lds, st, p);                             \
-    return mdf::check_launch("wgrad_lds_kernel");                                                                          \
-  }
-#define WG_LAUNCH(KHv, KWv, M3, Rv)                  \
-  {                                                  \
-    if (TH == 4) WG_LAUNCH_TH(KHv, KWv, M3, Rv, 4)   \
-    if (TH == 2) WG_LAUNCH_TH(KHv, KWv, M3, Rv, 2)   \
-    WG_LAUNCH_TH(KHv, KWv, M3, Rv, 1)                \
-  }
-  if (is3d && ksize == 3 && R == 2) WG_LAUNCH(3, 3, true, 2)
-  if (is3d && ksize == 3 && R == 1) WG_LAUNCH(3, 3, true, 1)
-  if (is3d && ksize == 3) WG_LAUNCH(3, 3, true, 0)
-  if (!is3d && ksize == 3 && R == 2) WG_LAUNCH(1, 3, false, 2)
-  if (!is3d && ksize == 3 && R == 1) WG_LAUNCH(1, 3, false, 1)
-  if (!is3d && ksize == 3) WG_LAUNCH(1, 3, false, 0)
-  if (!is3d && ksize == 5) WG_LAUNCH(1, 5, false, 0)
-  if (!is3d && ksize == 1) WG_LAUNCH(1, 1, false, 0)
-#undef WG_LAUNCH_TH
-#undef WG_LAUNCH
-  return MDF_EUNSUPPORTED;
+  const dim3 grid(gx, pl.gy, pl.gz);
+  mdf::note_wgrad_plan(0, R, TH, p.tv, p.n_tiles, gx, pl.gy, pl.gz, p.split);      // (a shape without an instantiation falls back: the direct form overwrites it)
+  const int rc = visit_inst(WgKey{KH, KW, is3d != 0, R, TH}, [&](auto inst) {
+    if (g_batching) {       // recorded: launched by mdf_wgrad_batch_flush together with the other layers of this instantiation
+      g_pending->push_back(PendingJob{inst.key, p, gx, pl.gy, pl.gz, lds});
+      return (int)MDF_OK;
+    }
+    return launch_lds<decltype(inst)::single>(grid, lds, (hipStream_t)stream, p, "wgrad_lds_kernel");
+  }, WgInsts{});
+  if (rc == MDF_OK) *gx_io = gx;
+  return rc;
 }

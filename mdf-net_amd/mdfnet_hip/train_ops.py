@@ -276,33 +276,42 @@ class _DeferredWgrad:
         return (self.work, self.dw_ptr, nslab.value, self.dw_numel), self.flops, 4.0 * (self.small.numel() + self.big.numel())
 
 
-def conv3d_wgrad(small, big, stride, out_shape, param=None):
-    """dw[a][b][27] = sum_o small[o][a] * big[stride*o + tap - 1][b]; small [B,Ds,Hs,Ws,A], big [B,s*Ds,..,Bc] NDHWC."""
+def _conv_wgrad(entry, workspace_entry, dims, small, big, dw_shape, flops, tag, param, hold=None):
+    """One layer's weight gradient through the C entry `entry` (mdf_conv3d_wgrad_partial / mdf_conv2d_wgrad_partial): the partial tiles go
+    to a workspace of `workspace_entry` floats and are summed into dw later (_sum_later), or -- inside a backward pass that may defer
+    -- the launch itself is put off to the end of the pass (_DeferredWgrad).  dims: the entry's integers between the pointers and
+    nslab_out; the workspace entry takes all but the last (the stride).  hold: see conv2d_wgrad."""
     _need_gpu(small, big)
-    b, ds, hs, ws, a = small.shape
-    bc = big.shape[-1]
-    assert tuple(big.shape[:4]) == (b, ds * stride, hs * stride, ws * stride), (small.shape, big.shape, stride)
     assert small.is_contiguous() and big.is_contiguous()
-    n = lib().mdf_conv3d_wgrad_workspace(b, ds, hs, ws, a, bc)
-    work = torch.empty(n, device=small.device, dtype=torch.float32)
-    dw = torch.empty(out_shape, device=small.device, dtype=torch.float32)
-    assert dw.numel() == a * bc * 27
-    if BATCH_WGRAD and _can_defer(param):
+    work = torch.empty(getattr(lib(), workspace_entry)(*dims[:-1]), device=small.device, dtype=torch.float32)
+    dw = torch.empty(dw_shape, device=small.device, dtype=torch.float32)
+    if BATCH_WGRAD and hold is None and _can_defer(param):
         ent = _pending_entry(dw.device.index, True)
         cur = torch.cuda.current_stream(dw.device)
         if cur not in ent[0]:
             ent[0].append(cur)
         dwp = dw.data_ptr()         # (the closure must not capture dw itself)
-        ent[2].append(_DeferredWgrad("mdf_conv3d_wgrad_partial", lambda ns, st: (small.data_ptr(), big.data_ptr(), dwp, work.data_ptr(), b, ds, hs, ws,
-                                                                                 a, bc, stride, ctypes.byref(ns), st),
-                                     small, big, dw, work, 2.0 * 27 * a * bc * b * ds * hs * ws))
+        ent[2].append(_DeferredWgrad(entry, lambda ns, st: (small.data_ptr(), big.data_ptr(), dwp, work.data_ptr(), *dims, ctypes.byref(ns), st),
+                                     small, big, dw, work, flops))
         return dw
     nslab = ctypes.c_int(0)
-    _abi("mdf_conv3d_wgrad_partial", (small.data_ptr(), big.data_ptr(), dw.data_ptr(), work.data_ptr(), b, ds, hs, ws, a, bc, stride,
-                                      ctypes.byref(nslab), _stream(dw)), tag=f"wgrad {a}x{bc} s{stride} {ds}x{hs}x{ws}",
-         work={"flops": 2.0 * 27 * a * bc * b * ds * hs * ws, "bytes": 4.0 * (small.numel() + big.numel()), "bound": "mfma"})
-    _sum_later(work, dw, nslab.value, dw.numel(), param)
+    _abi(entry, (small.data_ptr(), big.data_ptr(), dw.data_ptr(), work.data_ptr(), *dims, ctypes.byref(nslab), _stream(dw)), tag=tag,
+         work={"flops": flops, "bytes": 4.0 * (small.numel() + big.numel()), "bound": "mfma"})
+    if hold is not None:
+        hold.append((work, dw.data_ptr(), nslab.value, dw.numel()))
+    else:
+        _sum_later(work, dw, nslab.value, dw.numel(), param)
     return dw
+
+
+def conv3d_wgrad(small, big, stride, out_shape, param=None):
+    """dw[a][b][27] = sum_o small[o][a] * big[stride*o + tap - 1][b]; small [B,Ds,Hs,Ws,A], big [B,s*Ds,..,Bc] NDHWC."""
+    b, ds, hs, ws, a = small.shape
+    bc = big.shape[-1]
+    assert tuple(big.shape[:4]) == (b, ds * stride, hs * stride, ws * stride), (small.shape, big.shape, stride)
+    assert torch.Size(out_shape).numel() == a * bc * 27
+    return _conv_wgrad("mdf_conv3d_wgrad_partial", "mdf_conv3d_wgrad_workspace", (b, ds, hs, ws, a, bc, stride), small, big, out_shape,
+                       2.0 * 27 * a * bc * b * ds * hs * ws, f"wgrad {a}x{bc} s{stride} {ds}x{hs}x{ws}", param)
 
 
 def dgrad_pack(conv, transposed):
@@ -676,36 +685,16 @@ def conv2d_wgrad(small, big, ksize, stride, out_shape, param=None, hold=None):
     """dw[a][b][kh][kw] = sum_o small[o][a] * big[stride*o + (kh,kw) - pad][b]; small [B,Hs,Ws,A], big [B,s*Hs,s*Ws,Bc] NHWC.
     hold: a list -- the partial tiles are left un-summed and their job is appended to it; the caller sums several gradients it needs
     at once with ONE sum_wgrad_jobs(hold) (and must do so before reading any of them)."""
-    _need_gpu(small, big)
     b, hs, ws, a = small.shape
     bc = big.shape[-1]
     assert tuple(big.shape[:3]) == (b, hs * stride, ws * stride), (small.shape, big.shape, stride)
-    assert small.is_contiguous() and big.is_contiguous()
-    n = lib().mdf_conv2d_wgrad_workspace(b, hs, ws, a, bc, ksize)
-    work = torch.empty(n, device=small.device, dtype=torch.float32)
-    dw = torch.empty((a, bc, ksize, ksize), device=small.device, dtype=torch.float32)
-    if BATCH_WGRAD and hold is None and tuple(out_shape) == tuple(dw.shape) and _can_defer(param):
-        ent = _pending_entry(dw.device.index, True)
-        cur = torch.cuda.current_stream(dw.device)
-        if cur not in ent[0]:
-            ent[0].append(cur)
-        dwp = dw.data_ptr()         # (the closure must not capture dw itself)
-        ent[2].append(_DeferredWgrad("mdf_conv2d_wgrad_partial", lambda ns, st: (small.data_ptr(), big.data_ptr(), dwp, work.data_ptr(), b, hs, ws, a, bc,
-                                                                                 ksize, stride, ctypes.byref(ns), st),
-                                     small, big, dw, work, 2.0 * ksize * ksize * a * bc * b * hs * ws))
-        return dw
-    nslab = ctypes.c_int(0)
-    _abi("mdf_conv2d_wgrad_partial", (small.data_ptr(), big.data_ptr(), dw.data_ptr(), work.data_ptr(), b, hs, ws, a, bc, ksize, stride,
-                                      ctypes.byref(nslab), _stream(dw)), tag=f"wgrad2d {a}x{bc} k{ksize}s{stride} {hs}x{ws}x{b}",
-         work={"flops": 2.0 * ksize * ksize * a * bc * b * hs * ws, "bytes": 4.0 * (small.numel() + big.numel()), "bound": "mfma"})
-    if hold is not None:
-        assert tuple(out_shape) == tuple(dw.shape)
-        hold.append((work, dw.data_ptr(), nslab.value, dw.numel()))
-        return dw
-    _sum_later(work, dw, nslab.value, dw.numel(), param if tuple(out_shape) == tuple(dw.shape) else None)
-    if tuple(out_shape) != tuple(dw.shape):
-        pass     # (the image layer's weight gradient is computed over 4 padded input channels: summed at once, sliced below)
-    return dw if tuple(out_shape) == tuple(dw.shape) else dw[:, :out_shape[1]].contiguous()
+    # (the image layer's weight gradient is computed over 4 padded input channels: never deferred, summed at once, sliced below)
+    whole = tuple(out_shape) == (a, bc, ksize, ksize)
+    assert whole or hold is None
+    dw = _conv_wgrad("mdf_conv2d_wgrad_partial", "mdf_conv2d_wgrad_workspace", (b, hs, ws, a, bc, ksize, stride), small, big,
+                     (a, bc, ksize, ksize), 2.0 * ksize * ksize * a * bc * b * hs * ws, f"wgrad2d {a}x{bc} k{ksize}s{stride} {hs}x{ws}x{b}",
+                     param if whole else None, hold)
+    return dw if whole else dw[:, :out_shape[1]].contiguous()
 
 
 _K5_TAP = ((4, 2, 0), (-1, 3, 1))      # output parity p, 3x3 tap t -> 5x5 kernel index (-1: structurally zero)
