@@ -4,7 +4,13 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 #include "mdfnet_hip.h"
+
+template <int I, int N, typename F>   // f(integral_constant<int, i>) for i in [I, N): a loop whose index is a compile-time constant in the body
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
+}
 
 namespace mdf {
 

@@ -10,6 +10,7 @@
 // bit-identical to that path.
 #include <cstdlib>
 #include "common.h"
+#include "conv_dispatch.h"
 
 namespace {
 
@@ -293,8 +294,7 @@ int launch_1x1(P1& p, hipStream_t st) {
 
 }  // namespace
 
-// Internal entry used by mdf_conv2d_fwd for ksize 1, stride 1, NHWC input.  MDF_EUNSUPPORTED: no instantiation (the caller
-// falls back to the LDS kernels).
+// Internal entry (conv_dispatch.h) used by mdf_conv2d_fwd for ksize 1, stride 1, NHWC input; without an instantiation the caller falls back to the LDS kernels.
 #define C1_CASE(ci, co) \
   if (Cin == ci && Cout == co) return launch_1x1<ci, co>(p, (hipStream_t)stream);
 

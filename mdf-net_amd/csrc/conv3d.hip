@@ -24,6 +24,7 @@
 // bookkeeping and the epilogue are conv3d_common.h's; the transposed layers' own kernels are convtr3d.hip's.
 #include <cstdlib>
 #include "conv3d_common.h"
+#include "conv_dispatch.h"
 
 namespace {
 
@@ -522,13 +523,6 @@ int launch_conv_mt(ConvParams& p, hipStream_t st) {
 }  // namespace
 
 using mdf::ConvStat;
-
-int mdf_conv_lds_dispatch(const float* x, const float* wpack, const float* alpha, const float* beta, const float* res,
-                          float res_scale, const float* res_up, float* y, int B, int D, int H, int W, int Cin, int Cin_mem, int Cout, int KD,
-                          int KHW, int stride, int relu, void* stream, int planar_in, int shuffle2, const ConvStat* stat);      // conv_lds.hip
-
-int mdf_convtr3d_dispatch(const float* x, const float* wpack, const float* alpha, const float* beta, const float* res, float* y, int B,
-                          int Di, int Hi, int Wi, int Cin, int Cout, int relu, int kd_skip, void* stream);      // convtr3d.hip
 
 #define MDF_CONV_CASE(ci, co, mode)                          \
   if (Cin == ci && Cout == co && m == mode)                  \

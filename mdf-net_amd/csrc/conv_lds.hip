@@ -14,9 +14,9 @@
 // GEMM orientation is that of conv3d.hip, weight packing conv_pack.hip's:  D[cout][voxel] = W[cout][k] * X[k][voxel].
 #include <cstdlib>
 #include <mutex>
-#include <type_traits>
 #include "common.h"
 #include "conv_pack.h"
+#include "conv_dispatch.h"
 
 #include "conv_lds_common.h"
 
@@ -119,14 +119,6 @@ __device__ __forceinline__ void step(const float* const (&planes)[KD], __amdgpu_
       }
     }
     if constexpr (ST != 0) stat_commit<C::STAT_OFF>(lds_base_, c0, n16, ps, pq);
-  }
-}
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
   }
 }
 
@@ -336,18 +328,7 @@ __device__ __forceinline__ void step_wino(const float* const (&planes)[NKD], __a
 }
 
 template <int CIN, int CIN_MEM, int COUT, int KD, int KHW, int SHW, int MT, int RW = 1, int WG = 0, int ST = 0>
-// Register budget: the unrolled, pipelined tap loop wants ~280 registers (one 64-bit address pair per weight tap), which
-// leaves ONE wave per SIMD.  Capping at 256 (two resident blocks per CU) is worth 6-10 % for the single-n-tile kernels
-// (A/B in one process, scripts/bench_conv3d.py); with 2+ n-tiles the cap makes hipcc spill, so those stay uncapped.
-// (Tighter caps for the 2-D kernels were tried: they spill the MFMA-heavy ones and do not help the latency-bound ones.)
-// (Winograd form with 32+ input channels: its 141 KB of LDS allow one block per CU anyway, so it may use the whole register file)
-// (ST variants of the HBM-bound 2-D layers: the ~10 registers of the epilogue sums would cost an occupancy step -- 16->16 Winograd 26 -> 43 us,
-// 3->8 40 -> 58 us by rocprof -- so those keep their residency and spill a few registers instead)
-#ifndef MDF_WD8_BLOCKS
-#define MDF_WD8_BLOCKS 2
-#endif
-__global__ __launch_bounds__(256, (WG == 2 && CIN == 8) ? MDF_WD8_BLOCKS : (ST != 0 && KD == 1 && WG == 1 && CIN == 16) ? 3 : (ST != 0 && KD == 1 && CIN == 4) ? 4 :
-                                  ((COUT <= 16 && !(WG == 1 && CIN >= 32) && !(WG == 2 && CIN >= 16)) ? 2 : 1)) void conv_lds_kernel(const LdsConvParams p) {
+__global__ __launch_bounds__(256, lds_min_blocks(CIN, COUT, KD, WG, ST)) void conv_lds_kernel(const LdsConvParams p) {
   typedef Cfg<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG> C;
   constexpr int KPL = C::KPL, NG = C::NG, S = C::S, PW = C::PW, PH = C::PH;
   typedef typename VecT<KPL>::type vec_t;
@@ -760,19 +741,18 @@ __global__ __launch_bounds__(256, (WG == 2 && CIN == 8) ? MDF_WD8_BLOCKS : (ST !
   }
 }
 
-template <int CIN, int CIN_MEM, int COUT, int KD, int KHW, int SHW, int MT, int RW = 1, int WG = 0, int ST = 0>
-int launch_lds(LdsConvParams& p, hipStream_t st) {
-  typedef Cfg<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG> C;
-  constexpr size_t kLds = ST ? C::LDS_BYTES_ST : C::LDS_BYTES;
-  p.tiles_h = (p.Ho + C::TH - 1) / C::TH;
-  p.tiles_w = (p.Wo + C::TWO - 1) / C::TWO;
+// ---- the launch plan: fills the item space of one launch (p.tiles_h .. p.stat_slices) and returns its grid, or an error code (< 0)
+struct LdsGeom { int TH, TWO, KD, RD, NPL; bool STREAM, ST; size_t lds; };   // what it needs to know of a kernel: tile, depth step, epilogue sums or not, the LDS of that variant
+int plan_lds(const LdsGeom& g, LdsConvParams& p) {
+  p.tiles_h = (p.Ho + g.TH - 1) / g.TH;
+  p.tiles_w = (p.Wo + g.TWO - 1) / g.TWO;
   const long long tiles = (long long)p.B * p.tiles_h * p.tiles_w;
-  const int blocks_per_cu = (int)(160 * 1024 / kLds) < 1 ? 1 : (int)(160 * 1024 / kLds);
+  const int blocks_per_cu = (int)(160 * 1024 / g.lds) < 1 ? 1 : (int)(160 * 1024 / g.lds);
   const int max_grid = 256 * (blocks_per_cu > 4 ? 4 : blocks_per_cu);
   // 3-D: items = tile x depth chunk, handed out dynamically; aim for >= ~6 items per resident block (smooths the cheaper
   // partially-filled tile columns) while keeping >= 3 planes per chunk (prologue = KD-1 extra planes).
   // 2-D: one run of consecutive tiles per block (double-buffered inside the run), grid = min(tiles/2, resident blocks).
-  if (KD > 1) {
+  if (g.KD > 1) {
     // Depth-chunk length: ~6 items per resident block (the dynamic queue then evens out the cheaper, partially filled tile
     // columns), at least 3 planes per chunk (an item's prologue fetches KD-1 extra planes), chunks of equal length -- a
     // 1-plane tail chunk (D = 4 -> 3 + 1) costs a whole prologue for a third of the work: 93 -> 77 us on 16->16 @4x296x400.
@@ -780,14 +760,14 @@ int launch_lds(LdsConvParams& p, hipStream_t st) {
     // so fewer, longer items do not finish sooner.)
     // (one resident block and long pair steps: 179 -> 172 us on 16->8 @24x296x400 with 3; the three-plane ring form of that layer,
     //  two resident blocks: 163 us with 6, 158 with 4, 151 with 2)
-    long long ipb = C::STREAM ? 2 : ((C::RD == 2 && blocks_per_cu == 1) ? 3 : 6);
+    long long ipb = g.STREAM ? 2 : ((g.RD == 2 && blocks_per_cu == 1) ? 3 : 6);
     ipb = mdf::env_pos("MDF_CONV_ITEMS_PER_BLOCK", ipb);   // dev A/B
     long long want = (ipb * max_grid + tiles - 1) / tiles;
     if (want < 1) want = 1;
     if (want > p.D / 3) want = p.D / 3;
     if (want < 1) want = 1;
     int dch = (int)((p.D + want - 1) / want);
-    if (C::RD == 2 && (dch & 1)) ++dch;   // depth-pair form: whole pairs per chunk (an odd tail pair computes a plane it does not store)
+    if (g.RD == 2 && (dch & 1)) ++dch;   // depth-pair form: whole pairs per chunk (an odd tail pair computes a plane it does not store)
     // Between one and two rounds of resident blocks the second round runs mostly empty (32->32 @24x74x100: 40 tiles x 8 chunks = 320
     // items on 256 blocks took 98 us; x 6 chunks = 240 items: 74 us; 16->16 @12x148x200: 532 items on 512 blocks 50 us, 399 items 45 us):
     // lengthen the chunks until one round holds everything, if that round is shorter than the two it replaces.
@@ -797,16 +777,16 @@ int launch_lds(LdsConvParams& p, hipStream_t st) {
       //  or more rounds the dynamic queue fills the tail, and long chunks lose: 16->16 @48x148x200 130 -> 154 us)
       if (items0 > max_grid && items0 < 3 * (long long)max_grid) {
         const long long rounds0 = (items0 + max_grid - 1) / max_grid;
-        for (int d2 = dch + C::RD; d2 <= p.D + C::RD - 1; d2 += C::RD) {
+        for (int d2 = dch + g.RD; d2 <= p.D + g.RD - 1; d2 += g.RD) {
           if (tiles * ((p.D + d2 - 1) / d2) <= max_grid) {
-            if (10 * (d2 + C::NPL - 1) < 9 * rounds0 * (dch + C::NPL - 1)) dch = d2;
+            if (10 * (d2 + g.NPL - 1) < 9 * rounds0 * (dch + g.NPL - 1)) dch = d2;
             break;
           }
         }
       }
     }
     dch = mdf::env_pos("MDF_CONV_DCH", dch);   // dev A/B
-    if (C::RD == 2 && (dch & 1)) ++dch;   // depth-pair form: whole pairs per chunk (an odd tail pair computes a plane it does not store)
+    if (g.RD == 2 && (dch & 1)) ++dch;   // depth-pair form: whole pairs per chunk (an odd tail pair computes a plane it does not store)
     p.dch = dch;
     p.dchunks = (p.D + dch - 1) / dch;
     const long long items = tiles * p.dchunks;
@@ -819,19 +799,18 @@ int launch_lds(LdsConvParams& p, hipStream_t st) {
     p.tiles_per_item = 0;
     long long tpb = 2;   // small layers: residency (4 blocks/CU) beats long runs -- 30 -> 20 us on the refine-size convs (A/B)
     tpb = mdf::env_pos("MDF_CONV2D_TILES_PER_BLOCK", tpb);   // dev A/B
-    long long g = tiles / tpb;                   // >= tpb tiles per block
-    if (g < 256) g = 256;
-    if (g > max_grid) g = max_grid;
-    if (g > tiles) g = tiles;
-    p.n_items = (int)g;                          // = grid size (static partition)
+    long long n = tiles / tpb;                   // >= tpb tiles per block
+    if (n < 256) n = 256;
+    if (n > max_grid) n = max_grid;
+    if (n > tiles) n = tiles;
+    p.n_items = (int)n;                          // = grid size (static partition)
     p.dch = 1; p.dchunks = 1;
   }
-  if (int rc = mdf::ensure_dynamic_lds<&conv_lds_kernel<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, ST>>(kLds)) return rc;   // (one flag per instantiation, ST included)
   int grid = max_grid;
   grid = mdf::env_pos("MDF_CONV_GRID", grid);   // dev: residency experiments
   if (grid > p.n_items) grid = p.n_items;
-  if (ST) {
-    if (KD == 1) {   // groups x blocks-per-group
+  if (g.ST) {
+    if (g.KD == 1) {   // groups x blocks-per-group
       const int G = p.stat_groups > 0 ? p.stat_groups : 1;
       int bpg = grid / G;
       if (bpg < 1) bpg = 1;
@@ -841,23 +820,27 @@ int launch_lds(LdsConvParams& p, hipStream_t st) {
       p.stat_slices = mdf::conv_stat_slices(grid, p.stat_slices);
     }
   }
-  if (getenv("MDF_CONV_DEBUG")) {
-    int nb = -1;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv_lds_kernel<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, ST>, 256, kLds);
-    hipFuncAttributes fa{};
-    (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&conv_lds_kernel<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, ST>));
-    fprintf(stderr, "[conv_lds<%d,%d,%d,%d,%d,%d,%d,rw%d wg%d st%d>] LDS %zu B dyn + %zu static, regs %d, occupancy API: %d blocks/CU (%s), grid %d, items %d\n",
-            CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, ST, kLds, fa.sharedSizeBytes, fa.numRegs, nb, hipGetErrorString(e), grid, p.n_items);
-  }
-  hipLaunchKernelGGL((conv_lds_kernel<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, ST>), dim3(grid), dim3(256), kLds, st, p);
-  return mdf::check_launch("conv_lds_kernel");
+  return grid;
 }
 
-// the training-capable cases: the eval kernel, or the one with the epilogue sums of stat->mode (1 or 2)
-template <int CIN, int CIN_MEM, int COUT, int KD, int KHW, int SHW, int MT, int RW = 1, int WG = 0>
-int launch_lds_stat(LdsConvParams& p, hipStream_t st, const mdf::ConvStat* stat) {
-  if (!stat) return launch_lds<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, 0>(p, st);
-  return stat->mode == 1 ? launch_lds<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, 1>(p, st) : launch_lds<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, 2>(p, st);
+template <int CIN, int CIN_MEM, int COUT, int KD, int KHW, int SHW, int MT, int RW = 1, int WG = 0, int ST = 0>
+int launch_lds(LdsConvParams& p, hipStream_t st) {
+  typedef Cfg<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG> C;
+  constexpr LdsGeom g{C::TH, C::TWO, KD, C::RD, C::NPL, C::STREAM, ST != 0, ST ? C::LDS_BYTES_ST : C::LDS_BYTES};
+  constexpr auto kernel = &conv_lds_kernel<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, ST>;
+  const int grid = plan_lds(g, p);
+  if (grid < 0) return grid;
+  if (int rc = mdf::ensure_dynamic_lds<kernel>(g.lds)) return rc;   // (one flag per instantiation, ST included)
+  if (getenv("MDF_CONV_DEBUG")) {
+    int nb = -1;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 256, g.lds);
+    hipFuncAttributes fa{};
+    (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kernel));
+    fprintf(stderr, "[conv_lds<%d,%d,%d,%d,%d,%d,%d,rw%d wg%d st%d>] LDS %zu B dyn + %zu static, regs %d, occupancy API: %d blocks/CU (%s), grid %d, items %d\n",
+            CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, ST, g.lds, fa.sharedSizeBytes, fa.numRegs, nb, hipGetErrorString(e), grid, p.n_items);
+  }
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), g.lds, st, p);
+  return mdf::check_launch("conv_lds_kernel");
 }
 
 }  // namespace
@@ -873,16 +856,6 @@ extern "C" int mdf_debug_read_stamps(unsigned long long* out8, int reset) {
   return 0;
 }
 #endif
-
-// Internal entry used by mdf_conv3d_fwd (stride-1 3x3x3) and mdf_conv2d_fwd.  Returns MDF_EUNSUPPORTED when the
-// configuration has no LDS-kernel instantiation (caller falls back to conv v1 / reports the error).
-#define LDS_CASE(ci, cim, co, kd, k, s, mt)                                                      \
-  if (!stat && Cin == ci && Cin_mem == cim && Cout == co && KD == kd && KHW == k && stride == s) \
-    return launch_lds<ci, cim, co, kd, k, s, mt>(p, (hipStream_t)stream);
-// layers the training step runs raw with epilogue sums (forward statistics / backward reductions): both variants
-#define LDS_CASE_T(ci, cim, co, kd, k, s, mt)                                                    \
-  if (Cin == ci && Cin_mem == cim && Cout == co && KD == kd && KHW == k && stride == s)          \
-    return launch_lds_stat<ci, cim, co, kd, k, s, mt>(p, (hipStream_t)stream, stat);
 
 // stream -> scheduler slot (launches on one stream are ordered, so they can share a slot; different streams must not).
 // A slot stays bound to its stream handle until mdf_release_stream(stream) gives it back (long-lived processes that
@@ -911,47 +884,116 @@ extern "C" int mdf_release_stream(void* stream) {
   return MDF_OK;   // never used by a conv launch: nothing to release
 }
 
-// The forms below read a segment behind the plain fragments; conv_pack.h says where it lies and which sets carry it.  A case whose
-// set has no such segment does not launch (the dispatch goes on to the next form).
-// w-phase variants
-#define LDS_CASE_RW(ci, cim, co, kd, k, s, mt, nrw)                                              \
-  if (!stat && use_rw && Cin == ci && Cin_mem == cim && Cout == co && KD == kd && KHW == k && stride == s && !res_up && L.rw > 0) { \
-    p.wpack = wpack + L.rw_off();                                                                \
-    return launch_lds<ci, cim, co, kd, k, s, mt, nrw>(p, (hipStream_t)stream);                   \
+// ---- the dispatch: one ordered table ("conv_lds dispatch") ---------------------------------------------------------------
+namespace {
+struct LdsQuery {   // what a route is chosen by: the layer, what the call asks of the epilogue, and the switches
+  int Cin, Cin_mem, Cout, KD, KHW, stride, D, H, W, wd_mask;
+  bool stat, res, res_up, shuffle2, planar_in, use_wg, use_rw, wd_stream, k5w, k5w64, use_w3, use_w2;
+};
+// A form is the shape of a kernel's GEMM: direct taps; w-phase (Cout < 16: RW output voxels per MFMA column); Winograd F(2x2,3x3) in (h,w), 3-D
+// and 2-D; depth-pair Winograd (3-D, Cout 8) on a ring of 4 planes, and of 3 (eval).  The form owns the extra condition of its rows and the segment
+// of the packed set they read (conv_pack.h; a set without it does not launch): form_segment is its offset, or -1 where the condition does not hold.
+enum LdsForm { kPlain, kRw, kWg3, kWg2, kWd, kWdStream };
+long long form_segment(LdsForm f, const LdsQuery& q, const mdf::PackLayout& L) {
+  const bool wg = q.use_wg && !q.res_up && L.wino > 0;
+  const bool wd = q.use_wg && (q.wd_mask & (q.Cin == 8 ? 1 : 2)) && !q.res_up && q.D >= 2 && L.wd > 0;   // MDF_CONV_WD: bit 0 Cin 8, bit 1 Cin 16
+  if (f == kPlain) return 0;
+  if (f == kRw) return (q.use_rw && !q.res_up && L.rw > 0) ? L.rw_off() : -1;
+  // (2-D: the pixel-shuffle store is built into the two input-gradient kernels of the k5-s2 layers only)
+  if (f == kWg3 || f == kWg2) return (wg && (f == kWg3 || !q.shuffle2 || (q.Cin == 16 && q.Cout == 32) || (q.Cin == 32 && q.Cout == 64))) ? L.wino_off() : -1;
+  return (wd && (f == kWd || (q.wd_stream && !q.stat))) ? L.wd_off() : -1;   // kWd, kWdStream
+}
+// An entry of the table answers segment(q, L): the offset of what its kernel reads if it takes the layer, else -1; and launch().  A row is the kernel's
+// tuple (= the layer it takes), its form, and TRAIN: ST 1 / ST 2 kernels besides the eval one (PlainT / RwT: layers the training step runs with epilogue sums).
+template <LdsForm FORM, bool TRAIN, int CIN, int CIN_MEM, int COUT, int KD, int KHW, int SHW, int MT, int RW = 1, int WG = 0>
+struct LdsRow {
+  static long long segment(const LdsQuery& q, const mdf::PackLayout& L) {
+    return (q.Cin == CIN && q.Cin_mem == CIN_MEM && q.Cout == COUT && q.KD == KD && q.KHW == KHW && q.stride == SHW && (TRAIN || !q.stat)) ? form_segment(FORM, q, L) : -1;
   }
-#define LDS_CASE_RW_T(ci, cim, co, kd, k, s, mt, nrw)                                            \
-  if (use_rw && Cin == ci && Cin_mem == cim && Cout == co && KD == kd && KHW == k && stride == s && !res_up && L.rw > 0) { \
-    p.wpack = wpack + L.rw_off();                                                                \
-    return launch_lds_stat<ci, cim, co, kd, k, s, mt, nrw>(p, (hipStream_t)stream, stat);        \
+  static int launch(LdsConvParams& p, const LdsQuery& q, void* st) {   // the eval kernel, or the one with the epilogue sums of stat_mode (1 or 2)
+    constexpr auto st1 = &launch_lds<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, TRAIN ? 1 : 0>, st2 = &launch_lds<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, TRAIN ? 2 : 0>;
+    return (!q.stat ? &launch_lds<CIN, CIN_MEM, COUT, KD, KHW, SHW, MT, RW, WG, 0> : p.stat_mode == 1 ? st1 : st2)(p, (hipStream_t)st);
   }
+};
+template <int CI, int CIM, int CO, int KD, int K, int S, int MT> using Plain = LdsRow<kPlain, false, CI, CIM, CO, KD, K, S, MT>;
+template <int CI, int CIM, int CO, int KD, int K, int S, int MT> using PlainT = LdsRow<kPlain, true, CI, CIM, CO, KD, K, S, MT>;
+template <int CI, int CIM, int CO, int KD, int K, int S, int MT, int NRW> using Rw = LdsRow<kRw, false, CI, CIM, CO, KD, K, S, MT, NRW>;
+template <int CI, int CIM, int CO, int KD, int K, int S, int MT, int NRW> using RwT = LdsRow<kRw, true, CI, CIM, CO, KD, K, S, MT, NRW>;
+template <int CI, int CO> using Wg3 = LdsRow<kWg3, true, CI, CI, CO, 3, 3, 1, 1, 2, 1>;
+template <int CI, int CO> using Wg2 = LdsRow<kWg2, true, CI, CI, CO, 1, 3, 1, 1, 2, 1>;
+template <int CI> using Wd = LdsRow<kWd, true, CI, CI, 8, 3, 3, 1, 1, 2, 2>;
+template <int CI> using WdStream = LdsRow<kWdStream, false, CI, CI, 8, 3, 3, 1, 1, 2, 3>;
+// The k5 s2 layers as 3x3 Winograd convs over the four parity images of their input: wino2d.hip's S2D kernels, and the s2d form (CI -> CO on the 2-D Winograd kernel of 4*CI channels).
+bool s2d_ok(const LdsQuery& q, const mdf::PackLayout& L) {
+  return q.use_wg && q.k5w && q.KD == 1 && q.KHW == 5 && q.stride == 2 && !q.stat && !q.res_up && !q.shuffle2 && !q.planar_in && q.H % 2 == 0 && q.W % 2 == 0 && L.wino > 0;
+}
+template <int CI, int CO> struct S2d {
+  static long long segment(const LdsQuery& q, const mdf::PackLayout& L) { return (s2d_ok(q, L) && q.Cin == CI && q.Cin_mem == CI && q.Cout == CO) ? L.wino_off() : -1; }
+  static int launch(LdsConvParams& p, const LdsQuery&, void* st) { p.s2d = 1; return launch_lds<4 * CI, 4 * CI, CO, 1, 3, 1, 1, 2, 1>(p, (hipStream_t)st); }   // (the tile fill does the space-to-depth)
+};
+// The kernels of wino2d.hip and wino3d.hip (eval), entries at their place in the order; MDF_EUNSUPPORTED from them passes the layer on.
+struct Wino2dS2d {
+  static long long segment(const LdsQuery& q, const mdf::PackLayout& L) {
+    const bool pair = (q.Cin == 32 && q.Cout == 64 && q.k5w64) || (q.Cin == 16 && q.Cout == 32) || (q.Cin == 8 && q.Cout == 16);
+    return (s2d_ok(q, L) && q.use_w2 && !q.res && q.Cin == q.Cin_mem && pair) ? L.wino_off() : -1;
+  }
+  static int launch(LdsConvParams& p, const LdsQuery& q, void* st) { return mdf_wino2d_s2d_dispatch(p.x, p.wpack, p.alpha, p.beta, p.y, p.B, p.Ho, p.Wo, q.Cin, q.Cout, p.relu, st); }
+};
+template <int KD> struct WinoEval {   // KD 3: wino3d.hip, KD 1: wino2d.hip
+  static long long segment(const LdsQuery& q, const mdf::PackLayout& L) {
+    const bool own = KD == 3 ? (q.use_w3 && q.Cout % 16 == 0) : (q.use_w2 && !q.planar_in && q.D == 1);
+    return (q.use_wg && !q.stat && q.KD == KD && q.KHW == 3 && q.stride == 1 && q.Cin == q.Cin_mem && !q.res_up && !q.shuffle2 && L.wino > 0 && own) ? L.wino_off() : -1;
+  }
+  static int launch(LdsConvParams& p, const LdsQuery& q, void* st) {
+    if (KD == 3) return mdf_wino3d_dispatch(p.x, p.wpack, p.alpha, p.beta, p.res, p.res_scale, p.y, p.B, p.D, p.H, p.W, q.Cin, q.Cout, p.relu, st);
+    return mdf_wino2d_dispatch(p.x, p.wpack, p.alpha, p.beta, p.res, p.res_scale, p.y, p.B, p.H, p.W, q.Cin, q.Cout, p.relu, st);
+  }
+};
+// ---- THE table.  Order is priority: the first entry that takes the layer and has a kernel for it launches (launch_first: its rc).  A new layer is one line here.
+template <class... R> struct LdsList {
+  static int launch_first(const LdsQuery& q, const mdf::PackLayout& L, LdsConvParams& p, const float* wpack, void* stream) {
+    int rc = MDF_EUNSUPPORTED;
+    auto take = [&](auto row) {
+      const long long seg = row.segment(q, L);
+      if (seg < 0) return false;
+      p.wpack = wpack + seg;
+      return (rc = row.launch(p, q, stream)) != MDF_EUNSUPPORTED;
+    };
+    (void)(take(R{}) || ...);
+    return rc;
+  }
+};
+using LdsTable = LdsList<
+    // The 2-D k5 s2 layers as a Winograd 3x3 conv over the four parity images of their input (16 -> 32 is 64 -> 32: 16 instead of 25 MFMA groups
+    // per input channel, direct 163 -> 141 us; wino2d.hip then skips the groups whose weights are structurally zero, 12.25 per input channel:
+    // 140 -> 114 us, profiles/r07_bench_cfg2.md); the transform-domain fragments follow the 25 plain taps (conv_pack.h: k5w_built).  (8 -> 16
+    // and 32 -> 64 the same way; 32 -> 64 walks its 128 logical channels in two passes over the LDS plane of 64: direct 159 -> 127 us.  32 -> 16 over the parity images, measured 200 against 203 us -- that layer waits on HBM, and
+    // one block per CU does not help it.)
+    // (wino2d.hip's S2D form first: pinned accumulators, one transform cluster per chunk -- 16 -> 32 and, there only, 8 -> 16 and 32 -> 64)
+    Wino2dS2d, S2d<16, 32>,
+    Wd<8>, WdStream<16>, Wd<16>,   // 3-D stride-1 layers with 8 output channels: depth-pair Winograd
+    // eval: input-stationary Winograd, the 3-D stride-1 layers with 16 output channels (wino3d.hip) and the 2-D 3x3 stride-1 layers of the feature
+    // pyramid (wino2d.hip); same fragments as the Wg3 / Wg2 rows below
+    WinoEval<3>, WinoEval<1>,
+    Wg3<16, 16>, Wg3<32, 16>, Wg3<32, 32>, Wg3<16, 8>, Wg3<16, 32>,   // 3-D stride-1 layers with 16 output channels: Winograd F(2x2,3x3) in (h,w)
+    Wg2<16, 16>, Wg2<32, 32>, Wg2<64, 64>, Wg2<16, 32>, Wg2<32, 64>,
+    RwT<16, 16, 8, 3, 3, 1, 2, 2>, RwT<8, 8, 8, 3, 3, 1, 2, 2>, Rw<16, 16, 4, 1, 3, 1, 1, 4>, Rw<8, 8, 4, 1, 3, 1, 1, 4>,   // Cout < 16: w-phase form (RW output voxels per MFMA column)
+    RwT<8, 8, 8, 1, 3, 1, 2, 2>, RwT<4, 3, 8, 1, 3, 1, 2, 2>, Rw<4, 1, 8, 1, 3, 1, 2, 2>,   // also the HBM-bound ones: 64-B stores, half the LDS reads
+    // 3-D regulariser layers (stride 1)
+    Plain<32, 32, 16, 3, 3, 1, 2>, Plain<16, 16, 16, 3, 3, 1, 4>, Plain<16, 16, 8, 3, 3, 1, 4>, Plain<8, 8, 8, 3, 3, 1, 4>, Plain<32, 32, 32, 3, 3, 1, 2>,
+    Plain<16, 16, 32, 3, 3, 1, 2>, Plain<8, 8, 16, 3, 3, 1, 4>,      // input gradients of the regularisers' first layers (training)
+    // 2-D layers of the feature pyramid / refinement (KD = 1)
+    Plain<4, 3, 8, 1, 3, 1, 4>, Plain<8, 8, 8, 1, 3, 1, 4>, Plain<16, 16, 16, 1, 3, 1, 4>, Plain<32, 32, 32, 1, 3, 1, 2>, Plain<64, 64, 64, 1, 3, 1, 1>,
+    PlainT<8, 8, 16, 1, 5, 2, 2>, PlainT<16, 16, 32, 1, 5, 2, 2>, PlainT<32, 32, 64, 1, 5, 2, 1>,
+    Plain<16, 16, 32, 1, 1, 1, 4>, Plain<16, 16, 64, 1, 1, 1, 4>, Plain<32, 32, 64, 1, 1, 1, 2>, Plain<64, 64, 16, 1, 1, 1, 1>, Plain<64, 64, 32, 1, 1, 1, 1>,   // composed FPN heads (the first: training backward, B3^T)
+    Plain<64, 64, 64, 1, 1, 1, 1>, Plain<32, 32, 32, 1, 1, 1, 2>, Plain<32, 32, 16, 1, 1, 1, 2>, Plain<16, 16, 16, 1, 1, 1, 4>,
+    Plain<4, 1, 8, 1, 3, 1, 4>, Plain<8, 8, 32, 1, 3, 1, 4>, Plain<8, 8, 1, 1, 3, 1, 4>,
+    Plain<32, 32, 8, 1, 3, 1, 2>,                                       // input gradient of the refinement net's 8 -> 32 conv (training)
+    Plain<16, 16, 32, 1, 3, 1, 2>, Plain<32, 32, 64, 1, 3, 1, 1>,   // input gradients of the k5-s2 layers (training): 3x3 over dy, 4 parity classes as channels
+    Plain<16, 16, 4, 1, 3, 1, 4>, Plain<8, 8, 4, 1, 3, 1, 4>>;   // prob head as per-plane partial sums (prob_head.hip)
+}  // namespace
 
-// Winograd variants: the transform-domain weights
-#define LDS_CASE_WG(ci, co)                                                                      \
-  if (use_wg && KD == 3 && KHW == 3 && stride == 1 && Cin == ci && Cin_mem == ci && Cout == co && !res_up && L.wino > 0) { \
-    p.wpack = wpack + L.wino_off();                                                              \
-    return launch_lds_stat<ci, ci, co, 3, 3, 1, 1, 2, 1>(p, (hipStream_t)stream, stat);          \
-  }
-#define LDS_CASE_WG2(ci, co)                                                                     \
-  if (use_wg && KD == 1 && KHW == 3 && stride == 1 && Cin == ci && Cin_mem == ci && Cout == co && !res_up && L.wino > 0 && (!shuffle2 || (ci == 16 && co == 32) || (ci == 32 && co == 64))) { \
-    p.wpack = wpack + L.wino_off();                                                              \
-    return launch_lds_stat<ci, ci, co, 1, 3, 1, 1, 2, 1>(p, (hipStream_t)stream, stat);          \
-  }
-
-// depth-pair Winograd (3-D, Cout 8)
-#define LDS_CASE_WD(ci)                                                                          \
-  if (use_wd && KD == 3 && KHW == 3 && stride == 1 && Cin == ci && Cin_mem == ci && Cout == 8 && !res_up && D >= 2 && L.wd > 0) { \
-    p.wpack = wpack + L.wd_off();                                                                \
-    if (ci == 16 && wd_stream && !stat) return launch_lds<ci, ci, 8, 3, 3, 1, 1, 2, 3>(p, (hipStream_t)stream); \
-    return launch_lds_stat<ci, ci, 8, 3, 3, 1, 1, 2, 2>(p, (hipStream_t)stream, stat);           \
-  }
-
-int mdf_wino3d_dispatch(const float* x, const float* wpack_wino, const float* alpha, const float* beta, const float* res, float res_scale,
-                        float* y, int B, int D, int H, int W, int Cin, int Cout, int relu, void* stream);   // wino3d.hip
-int mdf_wino2d_dispatch(const float* x, const float* wpack_wino, const float* alpha, const float* beta, const float* res, float res_scale,
-                        float* y, int B, int H, int W, int Cin, int Cout, int relu, void* stream);
-int mdf_wino2d_s2d_dispatch(const float* x, const float* wpack_k5w, const float* alpha, const float* beta, float* y, int B, int Ho, int Wo,
-                            int Cin_mem, int Cout, int relu, void* stream);          // wino2d.hip
-
+// Used by mdf_conv3d_fwd (stride-1 3x3x3) and mdf_conv2d_fwd.  MDF_EUNSUPPORTED: no entry of the table takes the layer (the caller falls back to conv v1 / reports the error).
 int mdf_conv_lds_dispatch(const float* x, const float* wpack, const float* alpha, const float* beta, const float* res,
                           float res_scale, const float* res_up, float* y, int B, int D, int H, int W, int Cin, int Cin_mem, int Cout, int KD,
                           int KHW, int stride, int relu, void* stream, int planar_in, int shuffle2, const mdf::ConvStat* stat) {
@@ -977,67 +1019,14 @@ int mdf_conv_lds_dispatch(const float* x, const float* wpack, const float* alpha
   const int pad = (KHW - 1) / 2;
   p.Ho = (H + 2 * pad - KHW) / stride + 1;
   p.Wo = (W + 2 * pad - KHW) / stride + 1;
-  // The 2-D k5 s2 layers as a Winograd 3x3 conv over the four parity images of their input (16 -> 32 is 64 -> 32: 16 instead of 25 MFMA groups
-  // per input channel, direct 163 -> 141 us; wino2d.hip then skips the groups whose weights are structurally zero, 12.25 per input channel:
-  // 140 -> 114 us, profiles/r07_bench_cfg2.md); the transform-domain fragments follow the 25 plain taps (conv_pack.h: k5w_built).  (8 -> 16
-  // and 32 -> 64 the same way; 32 -> 64 walks its 128 logical channels in two passes over the LDS plane of 64: direct 159 -> 127 us.  32 -> 16 over the parity images, measured 200 against 203 us -- that layer waits on HBM, and
-  // one block per CU does not help it.)
-  if (use_wg && k5w && KD == 1 && KHW == 5 && stride == 2 && !stat && !res_up && !shuffle2 && !planar_in && H % 2 == 0 && W % 2 == 0 && L.wino > 0) {
-    // (wino2d.hip's S2D form first: pinned accumulators, one transform cluster per chunk -- 16 -> 32 and, there only, 8 -> 16 and 32 -> 64)
-    if (use_w2 && !res && Cin == Cin_mem && ((Cin == 32 && Cout == 64 && k5w64) || (Cin == 16 && Cout == 32) || (Cin == 8 && Cout == 16))) {
-      const int rc = mdf_wino2d_s2d_dispatch(x, wpack + L.wino_off(), alpha, beta, y, B, p.Ho, p.Wo, Cin, Cout, relu, stream);
-      if (rc != MDF_EUNSUPPORTED) return rc;
-    }
-    if (Cin == 16 && Cin_mem == 16 && Cout == 32) {
-      p.s2d = 1; p.wpack = wpack + L.wino_off();
-      return launch_lds<64, 64, 32, 1, 3, 1, 1, 2, 1>(p, (hipStream_t)stream);
-    }
-  }
   if (shuffle2 && Cout == 64 && !use_wg) return mdf::fail(MDF_EUNSUPPORTED, "pixel-shuffle store for Cout = 64 is built into the Winograd form only (MDF_CONV_WINOGRAD=0 is set)");
-  // 3-D stride-1 layers with 8 output channels: depth-pair Winograd
-  { const bool use_wd = use_wg && (wd_mask & 1); LDS_CASE_WD(8) }
-  { const bool use_wd = use_wg && (wd_mask & 2); LDS_CASE_WD(16) }
-  // 3-D stride-1 layers with 16 output channels, eval: input-stationary Winograd (wino3d.hip); same fragments as the form below
-  if (use_wg && use_w3 && !stat && KD == 3 && KHW == 3 && stride == 1 && Cin == Cin_mem && !res_up && !shuffle2 && Cout % 16 == 0 && L.wino > 0) {
-    const int rc = mdf_wino3d_dispatch(x, wpack + L.wino_off(), alpha, beta, res, res_scale, y, B, D, H, W, Cin, Cout, relu, stream);
-    if (rc != MDF_EUNSUPPORTED) return rc;
-  }
-  // 2-D 3x3 stride-1 layers of the feature pyramid, eval: wino2d.hip (same fragments as LDS_CASE_WG2 below)
-  if (use_wg && use_w2 && !stat && KD == 1 && KHW == 3 && stride == 1 && Cin == Cin_mem && !res_up && !shuffle2 && !planar_in && D == 1 && L.wino > 0) {
-    const int rc = mdf_wino2d_dispatch(x, wpack + L.wino_off(), alpha, beta, res, res_scale, y, B, H, W, Cin, Cout, relu, stream);
-    if (rc != MDF_EUNSUPPORTED) return rc;
-  }
-  // 3-D stride-1 layers with 16 output channels: Winograd F(2x2,3x3) in (h,w)
-  LDS_CASE_WG(16, 16) LDS_CASE_WG(32, 16) LDS_CASE_WG(32, 32) LDS_CASE_WG(16, 8) LDS_CASE_WG(16, 32)
-  LDS_CASE_WG2(16, 16) LDS_CASE_WG2(32, 32) LDS_CASE_WG2(64, 64) LDS_CASE_WG2(16, 32) LDS_CASE_WG2(32, 64)
-  // Cout < 16: w-phase form (RW output voxels per MFMA column)
-  LDS_CASE_RW_T(16, 16, 8, 3, 3, 1, 2, 2) LDS_CASE_RW_T(8, 8, 8, 3, 3, 1, 2, 2)
-  LDS_CASE_RW(16, 16, 4, 1, 3, 1, 1, 4) LDS_CASE_RW(8, 8, 4, 1, 3, 1, 1, 4)
-  LDS_CASE_RW_T(8, 8, 8, 1, 3, 1, 2, 2) LDS_CASE_RW_T(4, 3, 8, 1, 3, 1, 2, 2) LDS_CASE_RW(4, 1, 8, 1, 3, 1, 2, 2)   // also the HBM-bound ones: 64-B stores, half the LDS reads
-  // 3-D regulariser layers (stride 1)
-  LDS_CASE(32, 32, 16, 3, 3, 1, 2) LDS_CASE(16, 16, 16, 3, 3, 1, 4) LDS_CASE(16, 16, 8, 3, 3, 1, 4) LDS_CASE(8, 8, 8, 3, 3, 1, 4)
-  LDS_CASE(32, 32, 32, 3, 3, 1, 2)
-  LDS_CASE(16, 16, 32, 3, 3, 1, 2) LDS_CASE(8, 8, 16, 3, 3, 1, 4)      // input gradients of the regularisers' first layers (training)
-  // 2-D layers of the feature pyramid / refinement (KD = 1)
-  LDS_CASE(4, 3, 8, 1, 3, 1, 4) LDS_CASE(8, 8, 8, 1, 3, 1, 4) LDS_CASE(16, 16, 16, 1, 3, 1, 4) LDS_CASE(32, 32, 32, 1, 3, 1, 2)
-  LDS_CASE(64, 64, 64, 1, 3, 1, 1)
-  LDS_CASE_T(8, 8, 16, 1, 5, 2, 2) LDS_CASE_T(16, 16, 32, 1, 5, 2, 2) LDS_CASE_T(32, 32, 64, 1, 5, 2, 1)
-  LDS_CASE(16, 16, 32, 1, 1, 1, 4)      // composed FPN heads, training backward (B3^T)
-  LDS_CASE(16, 16, 64, 1, 1, 1, 4) LDS_CASE(32, 32, 64, 1, 1, 1, 2) LDS_CASE(64, 64, 16, 1, 1, 1, 1) LDS_CASE(64, 64, 32, 1, 1, 1, 1)
-  LDS_CASE(64, 64, 64, 1, 1, 1, 1)
-  LDS_CASE(32, 32, 32, 1, 1, 1, 2) LDS_CASE(32, 32, 16, 1, 1, 1, 2) LDS_CASE(16, 16, 16, 1, 1, 1, 4)   // composed FPN heads
-  LDS_CASE(4, 1, 8, 1, 3, 1, 4) LDS_CASE(8, 8, 32, 1, 3, 1, 4) LDS_CASE(8, 8, 1, 1, 3, 1, 4)
-  LDS_CASE(32, 32, 8, 1, 3, 1, 2)                                       // input gradient of the refinement net's 8 -> 32 conv (training)
-  LDS_CASE(16, 16, 32, 1, 3, 1, 2) LDS_CASE(32, 32, 64, 1, 3, 1, 1)   // input gradients of the k5-s2 layers (training): 3x3 over dy, 4 parity classes as channels
-  LDS_CASE(16, 16, 4, 1, 3, 1, 4) LDS_CASE(8, 8, 4, 1, 3, 1, 4)   // prob head as per-plane partial sums (prob_head.hip)
-  return MDF_EUNSUPPORTED;
+  const LdsQuery q{Cin, Cin_mem, Cout, KD, KHW, stride, D, H, W, wd_mask, stat != nullptr, res != nullptr, res_up != nullptr, shuffle2 != 0, planar_in != 0,
+                   use_wg, use_rw, wd_stream, k5w, k5w64, use_w3, use_w2};
+  return LdsTable::launch_first(q, L, p, wpack, stream);
 }
 
 // ---- the 2-D entry points -------------------------------------------------------------------------------------------------------
 using mdf::ConvStat, mdf::padded_cin;
-
-int mdf_conv1x1_dispatch(const float* x, const float* wpack, const float* alpha, const float* beta, const float* res, float res_scale,
-                         const float* res_up, float* y, int B, int H, int W, int Cin, int Cout, int relu, void* stream);      // conv1x1.hip
 
 static int conv2d_entry(const float* x, const float* wpack, const float* alpha, const float* beta, const float* res,
                         float res_scale, const float* res_up, float* y, int B, int H, int W, int Cin_mem, int Cout, int ksize, int stride,

@@ -3,7 +3,6 @@
 // has internal linkage: each translation unit gets its own copy.
 #pragma once
 #include <cstdlib>
-#include <type_traits>
 #include "common.h"
 #include "conv3d_common.h"      // f32x4, lds_add_f64 / row16_sum, the ST epilogue pair stat_accum / stat_commit
 
@@ -178,6 +177,23 @@ struct Cfg {
   static constexpr int STAT_OFF = EPI_OFF + 128, SAUX_OFF = STAT_OFF + 256;   // floats (STAT_OFF*4 is a multiple of 8)
   static constexpr size_t LDS_BYTES_ST = LDS_BYTES + 512 * sizeof(float);
 };
+
+// The min-blocks argument of conv_lds_kernel's __launch_bounds__(256, .), i.e. its register budget: the unrolled, pipelined tap loop wants ~280
+// registers (one 64-bit address pair per weight tap), which leaves ONE wave per SIMD.
+#ifndef MDF_WD8_BLOCKS
+#define MDF_WD8_BLOCKS 2
+#endif
+constexpr int lds_min_blocks(int cin, int cout, int kd, int wg, int st) {
+  if (wg == 2 && cin == 8) return MDF_WD8_BLOCKS;   // depth-pair Winograd form on 8 channels: a build-time A/B value
+  // ST variants of the HBM-bound 2-D layers: the ~10 registers of the epilogue sums would cost an occupancy step -- 16->16 Winograd 26 -> 43 us,
+  // 3->8 40 -> 58 us by rocprof -- so those keep their residency and spill a few registers instead
+  if (st != 0 && kd == 1 && wg == 1 && cin == 16) return 3;
+  if (st != 0 && kd == 1 && cin == 4) return 4;
+  // Capping at 256 (two resident blocks per CU) is worth 6-10 % for the single-n-tile kernels (A/B in one process, scripts/bench_conv3d.py); not
+  // the Winograd form with 32+ input channels: its 141 KB of LDS allow one block per CU anyway, so it may use the whole register file
+  if (cout <= 16 && !(wg == 1 && cin >= 32) && !(wg == 2 && cin >= 16)) return 2;
+  return 1;   // 2+ n-tiles: the cap makes hipcc spill.  (Tighter caps for the 2-D kernels were tried: they spill the MFMA-heavy ones and do not help the latency-bound ones.)
+}
 
 // The MFMA part of one output row-tile of one depth plane: MTL live m-tiles (16 voxels each) x all GEMM rows, accumulated into
 // acc (zeroed here).  Fully unrolled over the taps: LDS offsets are immediates, no bounds logic (halos are zero-filled in LDS).

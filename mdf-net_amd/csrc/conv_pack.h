@@ -55,7 +55,7 @@ MDF_HD constexpr PackLayout pack_layout(int is3d, int transposed, int Cin_mem, i
 // The offsets the readers carried as literals before this header existed, for the shapes that reach each reader.
 namespace pack_layout_check {
 constexpr long long up16(int c) { return ((c + 15) / 16) * 16; }
-// w-phase readers (conv_lds.hip LDS_CASE_RW / LDS_CASE_RW_T): kd*k*k*ci*16
+// w-phase readers (conv_lds.hip: the Rw / RwT rows): kd*k*k*ci*16
 static_assert(pack_layout(1, 0, 16, 8, 27).rw_off() == 27 * 16 * 16 && pack_layout(1, 0, 16, 8, 27).rw > 0, "rw 3-D 16->8");
 static_assert(pack_layout(1, 0, 8, 8, 27).rw_off() == 27 * 8 * 16 && pack_layout(1, 0, 8, 8, 27).rw > 0, "rw 3-D 8->8");
 static_assert(pack_layout(0, 0, 16, 4, 9).rw_off() == 9 * 16 * 16 && pack_layout(0, 0, 16, 4, 9).rw > 0, "rw 2-D 16->4");
@@ -63,15 +63,15 @@ static_assert(pack_layout(0, 0, 8, 4, 9).rw_off() == 9 * 8 * 16 && pack_layout(0
 static_assert(pack_layout(0, 0, 8, 8, 9).rw_off() == 9 * 8 * 16 && pack_layout(0, 0, 8, 8, 9).rw > 0, "rw 2-D 8->8");
 static_assert(pack_layout(0, 0, 3, 8, 9).rw_off() == 9 * 4 * 16 && pack_layout(0, 0, 3, 8, 9).rw > 0, "rw 2-D image layer, 3 channels");
 static_assert(pack_layout(0, 0, 1, 8, 9).rw_off() == 9 * 4 * 16 && pack_layout(0, 0, 1, 8, 9).rw > 0, "rw 2-D image layer, 1 channel");
-// 3-D Winograd (LDS_CASE_WG): 27*ci*up16(co) + (co == 8 ? 36*ci*16 : 0)
+// 3-D Winograd (the Wg3 rows): 27*ci*up16(co) + (co == 8 ? 36*ci*16 : 0)
 constexpr bool wg_ok(int ci, int co) {
   return pack_layout(1, 0, ci, co, 27).wino_off() == 27 * ci * up16(co) + (co == 8 ? 36 * ci * 16 : 0) && pack_layout(1, 0, ci, co, 27).wino > 0;
 }
 static_assert(wg_ok(16, 16) && wg_ok(32, 16) && wg_ok(32, 32) && wg_ok(16, 8) && wg_ok(16, 32), "3-D Winograd segment");
-// 2-D Winograd (LDS_CASE_WG2, and mdf_wino2d_dispatch over the same sets): 9*ci*up16(co)
+// 2-D Winograd (the Wg2 rows, and mdf_wino2d_dispatch over the same sets): 9*ci*up16(co)
 constexpr bool wg2_ok(int ci, int co) { return pack_layout(0, 0, ci, co, 9).wino_off() == 9 * ci * up16(co) && pack_layout(0, 0, ci, co, 9).wino > 0; }
 static_assert(wg2_ok(16, 16) && wg2_ok(32, 32) && wg2_ok(64, 64) && wg2_ok(16, 32) && wg2_ok(32, 64), "2-D Winograd segment");
-// depth-pair Winograd (LDS_CASE_WD): 27*ci*16 + 36*ci*16 + (ci == 16 ? 3*16*64*4 : 0)
+// depth-pair Winograd (the Wd / WdStream rows): 27*ci*16 + 36*ci*16 + (ci == 16 ? 3*16*64*4 : 0)
 static_assert(pack_layout(1, 0, 8, 8, 27).wd_off() == 27 * 8 * 16 + 36 * 8 * 16 && pack_layout(1, 0, 8, 8, 27).wd > 0, "depth-pair 8->8");
 static_assert(pack_layout(1, 0, 16, 8, 27).wd_off() == 27 * 16 * 16 + 36 * 16 * 16 + 3 * 16 * 64 * 4 && pack_layout(1, 0, 16, 8, 27).wd > 0, "depth-pair 16->8");
 // k5 s2 over the parity images, wino2d.hip form: 25 taps x NCH x NT x 64 lanes x KPL

@@ -12,7 +12,6 @@
 // A strip is 62 pixels because its intermediate row is then 64 = 2 MFMA tiles (a 64-pixel strip would need 66: a third,
 // almost empty tile per row of layer 1).
 #include <cstdlib>
-#include <type_traits>
 #include "common.h"
 #include "conv_pack.h"
 
@@ -234,14 +233,6 @@ __device__ __forceinline__ float dpp_from_right(float v) {   // lane i <- lane i
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
 }
 
-template <int I, int N, typename F>
-__device__ __forceinline__ void pv_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    pv_static_for<I + 1, N>(f);
-  }
-}
-
 #ifndef MDF_PAIRV_BLOCKS
 #define MDF_PAIRV_BLOCKS 1
 #endif
@@ -301,7 +292,7 @@ __global__ __launch_bounds__(256, MDF_PAIRV_BLOCKS) void conv_pair_valu_kernel(c
       f8s wa[3], wb[3];
       asm volatile("s_load_dwordx8 %0, %3, 0x0\n\ts_load_dwordx8 %1, %3, 0x40\n\ts_load_dwordx8 %2, %3, 0x80"
                    : "=&s"(wa[0]), "=&s"(wa[1]), "=&s"(wa[2]) : "s"(w1_));
-      pv_static_for<0, 9>([&](auto tc) {
+      static_for<0, 9>([&](auto tc) {
         constexpr int tap = decltype(tc)::value, kh = tap / 3, kw = tap % 3;
         constexpr int SL = (P + kh) % 3;
         f8s (&cur)[3] = (tap & 1) ? wb : wa;
@@ -348,7 +339,7 @@ __global__ __launch_bounds__(256, MDF_PAIRV_BLOCKS) void conv_pair_valu_kernel(c
       // previous group's FMAs: left free, the scheduler runs the loads ahead and parks ~2000 scalar registers in vector lanes.
       f16s wa0, wa1, wb0, wb1;
       asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx16 %1, %2, 0x80" : "=&s"(wa0), "=&s"(wa1) : "s"(w2_));
-      pv_static_for<0, 18>([&](auto gc) {
+      static_for<0, 18>([&](auto gc) {
         constexpr int g = decltype(gc)::value, tap = g / 2, h = g % 2, kh = tap / 3, kw = tap % 3;
         constexpr int SL = (P + 1 + kh) % 3;
         f16s& c0 = (g & 1) ? wb0 : wa0;
@@ -402,7 +393,7 @@ __global__ __launch_bounds__(256, MDF_PAIRV_BLOCKS) void conv_pair_valu_kernel(c
 }  // namespace
 
 // weights: the packings mdf_conv_pack_weights produces for (Cin_mem 3, Cout 8, 9 taps) and (8, 8, 9 taps).  conv_pair_kernel reads
-// their w-phase segments (conv_pack.h: rw_off(), as conv_lds.hip's LDS_CASE_RW does)
+// their w-phase segments (conv_pack.h: rw_off(), as conv_lds.hip's w-phase rows do)
 extern "C" int mdf_conv2d_pair_fwd(const float* x, const float* w1pack, const float* alpha1, const float* beta1, const float* w2pack,
                                    const float* alpha2, const float* beta2, float* y, int N, int H, int W, void* stream) {
   MDF_REQUIRE(x && w1pack && alpha1 && beta1 && w2pack && alpha2 && beta2 && y, "null pointer argument");

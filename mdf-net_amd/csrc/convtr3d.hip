@@ -4,6 +4,7 @@
 // keep; conv3d_common.h the shared voxel bookkeeping and epilogue; mdf_convtr3d_dispatch below the route rules.
 #include <cstdlib>
 #include "conv3d_common.h"
+#include "conv_dispatch.h"
 
 namespace {
 
@@ -319,8 +320,7 @@ int launch_convtr_all(ConvParams& p, hipStream_t st) {
 
 }  // namespace
 
-// Internal entry used by conv3d_entry (conv3d.hip) for the transposed layers of the eval path.  Returns MDF_EUNSUPPORTED when no rule
-// below takes the layer (the caller goes on to conv3d_kernel<kTr>).
+// Internal entry (conv_dispatch.h) used by conv3d_entry for the transposed layers of the eval path; where no rule below takes the layer the caller goes on to conv3d_kernel<kTr>.
 int mdf_convtr3d_dispatch(const float* x, const float* wpack, const float* alpha, const float* beta, const float* res, float* y, int B,
                           int Di, int Hi, int Wi, int Cin, int Cout, int relu, int kd_skip, void* stream) {
   ConvParams p = conv_params(x, wpack, alpha, beta, res, y, B, Di, Hi, Wi, kTr, relu, kd_skip, nullptr);

@@ -197,7 +197,7 @@ extern "C" int mdf_prob_fused_fwd(const float* x, const float* wpack, const floa
   MDF_REQUIRE((long long)B * D * h * wd * Cin < (1ll << 31), "input too large for 32-bit offsets");
   ProbParams p{};
   p.x = x; p.hypos = hypos; p.per_pixel = hypos_per_pixel; p.prob = prob; p.depth = depth; p.B = B; p.D = D; p.H = h; p.W = wd;
-  const mdf::PackLayout L = mdf::pack_layout(0, 0, Cin, 4, 9);      // the prob-slices set: the kernel reads its w-phase segment, as LDS_CASE_RW does
+  const mdf::PackLayout L = mdf::pack_layout(0, 0, Cin, 4, 9);      // the prob-slices set: the kernel reads its w-phase segment, as conv_lds.hip's w-phase rows do
   if (L.rw == 0) return mdf::fail(MDF_EUNSUPPORTED, "fused prob head: the packed set of Cin=%d has no w-phase segment", Cin);
   p.wpack = wpack + L.rw_off();
   if (Cin == 8) return launch_prob_fused<8, 4>(p, (hipStream_t)stream);

@@ -226,7 +226,7 @@ extern "C" int mdf_refine_head_fwd(const float* depth, const float* lo, const fl
 }
 
 // weights: the packings mdf_conv_pack_weights produces for (Cin_mem 8, Cout 8, 9 taps); the kernel reads their w-phase segments
-// (conv_pack.h: rw_off(), as conv_lds.hip's LDS_CASE_RW and conv_pair.hip do)
+// (conv_pack.h: rw_off(), as conv_lds.hip's w-phase rows and conv_pair.hip do)
 extern "C" int mdf_conv2d_res_pair_fwd(const float* x, const float* wa_pack, const float* wb_pack, float scale, float* y, int N, int H,
                                        int W, void* stream) {
   MDF_REQUIRE(x && wa_pack && wb_pack && y, "null pointer argument");

@@ -30,19 +30,12 @@
 #include <cstdlib>
 #include <type_traits>
 #include "common.h"
+#include "conv_dispatch.h"
 #include "conv_lds_common.h"
 #define W3_PINNED_TILES_32      // 2 cout tiles x 16 transform-domain elements per wave: a[64:191] pinned, a[192:255] stay with the compiler
 #include "wino3d_acc.h"
 
 namespace {
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
 
 struct Wino2dParams {
   const float* x;      // [B,H,W,CIN]; S2D: [B,2H,2W,CIN/4]

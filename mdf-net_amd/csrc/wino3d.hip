@@ -20,18 +20,11 @@
 #include <cstdlib>
 #include <type_traits>
 #include "common.h"
+#include "conv_dispatch.h"
 #include "conv_lds_common.h"
 #include "wino3d_acc.h"
 
 namespace {
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
 
 struct Wino3dParams {
   const float* x;      // [B,D,H,W,CIN]
