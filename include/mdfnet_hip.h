@@ -116,6 +116,16 @@ int mdf_conv3d_fwd(const float* x, const float* wpack, const float* alpha, const
                    float* y, int B, int Di, int Hi, int Wi, int Cin, int Cout, int stride, int transposed,
                    int relu, void* stream);
 
+/* The depth-preserving sampling layers of RegularNet_4Scales(sample_stride=(1,2,2), sample_padding=(0,1,1))
+ * (net/unit/regular.py:76-77), same operands, layouts, epilogue and return codes as mdf_conv3d_fwd:
+ *   transposed = 0: Conv3d(k3, stride (1,2,2), pad 1)            Do = Di, Ho = (Hi-1)/2+1, Wo = (Wi-1)/2+1
+ *   transposed = 1: ConvTranspose3d(k3, stride (1,2,2), pad 1, output_padding (0,1,1))   Do = Di, Ho = 2Hi, Wo = 2Wi
+ *   wpack    from mdf_conv3d_pack_weights with the same `transposed` (no packing of its own)
+ *   (Cin,Cout) in {(8,16),(16,32),(32,64)} (transposed = 0), {(64,32),(32,16),(16,8)} (transposed = 1).  Eval only. */
+int mdf_conv3d_hw2_fwd(const float* x, const float* wpack, const float* alpha, const float* beta, const float* res,
+                       float* y, int B, int Di, int Hi, int Wi, int Cin, int Cout, int transposed, int relu,
+                       void* stream);
+
 /* Packed-weight size in floats for a (Cin,Cout) k=3 layer. */
 int64_t mdf_conv3d_packed_size(int Cin, int Cout);
 /* Re-order torch weights into the MFMA B-fragment order (device -> device, on `stream`).

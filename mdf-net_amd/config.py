@@ -207,7 +207,32 @@ def _atv_args(scales):
     return [1.5] + list(scales)
 
 
-def build_model(aggregate="vector", curves=None, prob_thresh=None, confidence="last", atv_scale=None):
+REGULAR_STRIDES = {(2, 2, 2): (1, 1, 1), (1, 2, 2): (0, 1, 1)}     # sample_stride -> sample_padding of the RegularNet_4Scales slots
+
+
+def parse_stride(text):
+    """ "1,2,2" -> (1, 2, 2)  (the --regular_stride flag of eval.py / validate.py), checked."""
+    try:
+        stride = tuple(int(p) for p in text.split(","))
+    except ValueError:
+        stride = None
+    if stride not in REGULAR_STRIDES:
+        raise ValueError(f"regular_stride={text!r}: choose one of {['%d,%d,%d' % s for s in REGULAR_STRIDES]}")
+    return stride
+
+
+def _regular_stride_args(stride):
+    """-> (sample_stride, sample_padding) of the two RegularNet_4Scales slots, checked."""
+    try:
+        stride = tuple(int(v) for v in stride)
+    except (TypeError, ValueError):
+        raise ValueError(f"regular_stride={stride!r}: choose one of {tuple(REGULAR_STRIDES)}") from None
+    if stride not in REGULAR_STRIDES:
+        raise ValueError(f"regular_stride={stride!r}: choose one of {tuple(REGULAR_STRIDES)}")
+    return stride, REGULAR_STRIDES[stride]
+
+
+def build_model(aggregate="vector", curves=None, prob_thresh=None, confidence="last", atv_scale=None, regular_stride=(2, 2, 2)):
     """A fresh CoreNet.  curves: the curve HyposByFit fits before stages 1 and 2, default ("gauss1", "laplace"); prob_thresh: their
     thresholds, default (0.95, 1e-5).  "atv" in a stage is the adaptive-thin-volume range of the reference's atv_hypos instead of a
     curve fit: it reads atv_scale (a pair, default (1.5, 1.5), each finite and > 0) and ignores its prob_thresh (still checked); its
@@ -219,13 +244,18 @@ def build_model(aggregate="vector", curves=None, prob_thresh=None, confidence="l
     the vector model) do not load into it.  confidence="last" (default): the confidence map comes from the last stage's probability
     volume alone, as the reference's config composes it.  confidence="cascade": regress.confidence_cascade in the slot -- every stage
     blends 0.8 * bicubic x2 of the previous stage's confidence with 0.2 of its own (regress.py:20-23), eval only; the slot has no
-    parameters, so the state_dict is the same."""
+    parameters, so the state_dict is the same.  regular_stride=(2,2,2) (default): the reference's composition.  regular_stride=(1,2,2):
+    both RegularNet_4Scales slots (stages 1 and 2) are composed with sample_stride (1,2,2), sample_padding (0,1,1) -- the alternative
+    the reference names at regular.py:76-77: the U-Net halves H and W and keeps every depth plane.  Same state_dict (3x3x3 kernels
+    either way): a checkpoint trained with the reference's (1,2,2) composition loads strictly; one trained for (2,2,2) loads too but
+    was not trained for it.  Eval only on the GPU.  RegularNet_3Scales (stage 0) has no such option in the reference."""
     if aggregate not in AGGREGATES:
         raise ValueError(f"aggregate={aggregate!r}: choose one of {AGGREGATES}")
     if confidence not in CONFIDENCES:
         raise ValueError(f"confidence={confidence!r}: choose one of {CONFIDENCES}")
     cv, th = _curve_args(curves, prob_thresh)
     sc = _atv_args(atv_scale)
+    rs, rp = _regular_stride_args(regular_stride)
     hypos = nn.ModuleList([HyposByFit(ndepths[i], cv[i], th[i], atv_scale=sc[i]) for i in range(stages - 1)])
     if aggregate == "variance":
         from net.unit.homoaggregate import homo_aggregate_by_variance
@@ -234,7 +264,7 @@ def build_model(aggregate="vector", curves=None, prob_thresh=None, confidence="l
     else:
         aggre = nn.ModuleList([VectorAggregate(ngroups[i]) for i in range(stages - 1)])
         in_chs = ngroups
-    regular = nn.ModuleList([RegularNet_3Scales(in_chs[0])] + [RegularNet_4Scales(c) for c in in_chs[1:]])
+    regular = nn.ModuleList([RegularNet_3Scales(in_chs[0])] + [RegularNet_4Scales(c, sample_stride=rs, sample_padding=rp) for c in in_chs[1:]])
     return core.CoreNet(backbone.FPN_4Scales(chs), hypos, scale, aggre, regular,
                         [regress.depth_regression, regress.confidence_cascade if confidence == "cascade" else regress.confidence_regress],
                         refine.RefineNet2())

@@ -96,7 +96,7 @@ def run_eval(model, dataset, device, output_path, rank=0, world=1, nworks=1, log
     return len(idx), time.time() - t_begin
 
 
-def main():
+def build_parser():
     import config
     parser = argparse.ArgumentParser(description="eval parameter setting")
     parser.add_argument("-p", "--pre_model", default=None, type=str, help="Pre training model")
@@ -115,7 +115,15 @@ def main():
     parser.add_argument("--scene_root", default=None, type=str, help="-d scene: the folder tools/colmap/main.py wrote its scenes into")
     parser.add_argument("--scenes", default="", type=str, help="-d scene: comma-separated scene folders under --scene_root")
     parser.add_argument("--nviews", default=5, type=int, help="-d scene: views per item (the reference view and its best sources)")
-    args = parser.parse_args()
+    parser.add_argument("--regular_stride", default="2,2,2", type=str, choices=["2,2,2", "1,2,2"],
+                        help="sample stride of the stage-1/2 regularisers the checkpoint was trained with: 2,2,2 (the reference's composition) "
+                             "or 1,2,2 (its depth-preserving alternative: H and W are halved, every depth plane is kept)")
+    return parser
+
+
+def main():
+    import config
+    args = build_parser().parse_args()
     logging.info(args)
     rank, world, local = shard.init()
     if args.dataset == "dtu":
@@ -136,10 +144,11 @@ def main():
         dataset = LoadDataset(datasetpath=load_args.eval_root, scenelist=load_args.scenelist, nviews=eval_args.nviews)
     curves, thresh = config.parse_pair(args.curves, str), config.parse_pair(args.prob_thresh, float)
     atv_scale = config.parse_pair(args.atv_scale, float)
+    regular_stride = config.parse_stride(args.regular_stride)
     default = args.aggregate == "vector" and curves == tuple(config.curve_calss[1:]) and thresh == tuple(config.prob_thresh[1:]) \
-        and args.confidence == "last"
+        and args.confidence == "last" and regular_stride == (2, 2, 2)
     model = config.model if default else config.build_model(aggregate=args.aggregate, curves=curves, prob_thresh=thresh, atv_scale=atv_scale,
-                                                            confidence=args.confidence)
+                                                            confidence=args.confidence, regular_stride=regular_stride)
     if args.pre_model is not None:
         model.load_state_dict(torch.load(args.pre_model, map_location="cpu")["model"])
     model.to(eval_args.DEVICE)

@@ -38,6 +38,7 @@ SIGNATURES = {
     "mdf_warp_aggregate_var_fwd": (c_int, [c_fp, ctypes.POINTER(c_fp), c_int, c_fp, c_fp, c_int, c_fp, c_int]
                                    + [c_int] * 6 + [c_fp]),
     "mdf_conv3d_fwd": (c_int, [c_fp] * 6 + [c_int] * 9 + [c_fp]),
+    "mdf_conv3d_hw2_fwd": (c_int, [c_fp] * 6 + [c_int] * 8 + [c_fp]),
     "mdf_conv3d_packed_size": (c_i64, [c_int, c_int]),
     "mdf_conv3d_pack_weights": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp]),
     "mdf_conv2d_fwd": (c_int, [c_fp] * 5 + [ctypes.c_float, c_fp, c_fp] + [c_int] * 10 + [c_fp]),

@@ -25,6 +25,7 @@ KERNEL_FAMILY = {
     "conv_lds_kernel": MFMA_CONV, "conv3d_kernel": MFMA_CONV, "conv3d_wlds_kernel": MFMA_CONV, "convtr_all_kernel": MFMA_CONV, "convtr_cls_kernel": MFMA_CONV, "conv_pair_kernel": MFMA_CONV, "conv_pair_valu_kernel": MFMA_CONV,   # (the pair on packed fp32 FMAs: same layers, same family)
     "conv1x1_kernel": MFMA_CONV, "conv1x1_heads_kernel": MFMA_CONV, "refine_tail_kernel": MFMA_CONV, "prob_fused_kernel": MFMA_CONV, "res_pair_kernel": MFMA_CONV,
     "wino3d_kernel": MFMA_CONV, "wino2d_kernel": MFMA_CONV,
+    "conv3d_hw_kernel": MFMA_CONV,   # conv3d_hw.hip: the (1,2,2) sampling layers (mdf_conv3d_hw2_fwd)
     "pack_weights_kernel": CONTROL, "pack_batch_kernel": CONTROL,
     # warp_aggregate.hip
     "warp_kernel": WARP, "warp_vec8_kernel": WARP, "warp_pairdiff_kernel": WARP, "warp_vec_win_kernel": WARP, "corner_index_kernel": WARP,

@@ -532,7 +532,12 @@ def pack_conv3d_weight(w, transposed=False):
 
 
 def conv3d_ndhwc(x, wpack, cin, cout, stride=1, transposed=False, alpha=None, beta=None, relu=False, res=None):
-    """y = [res +] [relu](conv(x)*alpha + beta).  x [B,D,H,W,Cin] contiguous -> y [B,Do,Ho,Wo,Cout]."""
+    """y = [res +] [relu](conv(x)*alpha + beta).  x [B,D,H,W,Cin] contiguous -> y [B,Do,Ho,Wo,Cout].  stride: 1 or 2 on every
+    axis, or the tuple (1,2,2) -- the depth-preserving sampling layers (mdf_conv3d_hw2_fwd): Do = D, Ho, Wo as for stride 2."""
+    if not isinstance(stride, int):
+        if tuple(stride) != (1, 2, 2):
+            raise ValueError(f"conv3d_ndhwc: stride is 1, 2 or the tuple (1,2,2), got {tuple(stride)}")
+        return _conv3d_hw2(x, wpack, cin, cout, transposed, alpha, beta, relu, res)
     _need_gpu(x, wpack)
     b, d, h, w, c = x.shape
     assert c == cin and x.is_contiguous()
@@ -552,6 +557,32 @@ def conv3d_ndhwc(x, wpack, cin, cout, stride=1, transposed=False, alpha=None, be
          work={"flops": 2.0 * 27 * cin * cout * b * (d * h * w if transposed else do * ho * wo),
                "bytes": 4.0 * (x.numel() + y.numel() * (2 if res is not None else 1)), "bound": "mfma"})
     return y
+
+
+def _conv3d_hw2(x, wpack, cin, cout, transposed, alpha, beta, relu, res):
+    """conv3d_ndhwc with stride (1,2,2): Conv3d(k3, (1,2,2), pad 1), or ConvTranspose3d(k3, (1,2,2), pad 1, output_padding (0,1,1)),
+    on the weight set pack_conv3d_weight(w, transposed) made (mdf_conv3d_hw2_fwd)."""
+    _need_gpu(x, wpack)
+    b, d, h, w, c = x.shape
+    assert c == cin and x.is_contiguous()
+    ho, wo = (2 * h, 2 * w) if transposed else ((h - 1) // 2 + 1, (w - 1) // 2 + 1)
+    y = torch.empty((b, d, ho, wo, cout), device=x.device, dtype=torch.float32)
+    if res is not None:
+        assert res.shape == y.shape and res.is_contiguous()
+    _abi("mdf_conv3d_hw2_fwd", (x.data_ptr(), wpack.data_ptr(), None if alpha is None else alpha.data_ptr(),
+                                None if beta is None else beta.data_ptr(), None if res is None else res.data_ptr(),
+                                y.data_ptr(), b, d, h, w, cin, cout, int(transposed), int(relu), _stream(y),),
+         tag=f"{cin}->{cout} {'T' if transposed else 's'}122 {d}x{h}x{w}",
+         work={"flops": conv3d_hw2_flops(b, d, h, w, cin, cout, transposed),
+               "bytes": 4.0 * (x.numel() + y.numel() * (2 if res is not None else 1)), "bound": "mfma"})
+    return y
+
+
+def conv3d_hw2_flops(b, d, h, w, cin, cout, transposed):
+    """Multiply-adds x 2 the (1,2,2) layer needs on a [b,d,h,w] input: 27 taps per output voxel (down); per INPUT voxel the three depth
+    taps of all nine (kh, kw) pairs (up: every weight meets every input voxel once, borders aside)."""
+    vox = b * d * h * w if transposed else b * d * ((h - 1) // 2 + 1) * ((w - 1) // 2 + 1)
+    return 2.0 * 27 * cin * cout * vox
 
 
 STAT_SLICES = 16      # copies of the epilogue sums a conv launch spreads its blocks over (the BatchNorm kernels add them up)

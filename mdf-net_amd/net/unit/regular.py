@@ -29,7 +29,8 @@ def run_layer(block, x, res=None, tape=None):
     tensors = [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var]
     wpack, alpha, beta = _cache(conv).get(tensors, lambda: (ops.pack_conv3d_weight(conv.weight, tr),)
                                           + ops.fold_bn(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps))
-    stride = conv.stride[0]
+    stride = tuple(conv.stride)      # (1,1,1) / (2,2,2): the int form of ops.conv3d_ndhwc; (1,2,2): the depth-preserving layers
+    stride = stride[0] if stride[0] == stride[1] == stride[2] else stride
     return ops.conv3d_ndhwc(x, wpack, conv.in_channels, conv.out_channels, stride, tr, alpha, beta, True, res)
 
 
@@ -88,12 +89,16 @@ class RegularNet_3Scales(nn.Module):
 
 
 class RegularNet_4Scales(nn.Module):
-    """Stage-1/2 regulariser (regular.py:72-133): 8/16/32/64-channel 4-level U-Net -> softmax over D."""
+    """Stage-1/2 regulariser (regular.py:72-133): 8/16/32/64-channel 4-level U-Net -> softmax over D.  sample_stride (2,2,2) with
+    sample_padding (1,1,1) halves D, H and W per level (D % 8 == 0); (1,2,2) with (0,1,1) -- the alternative the reference names at
+    regular.py:76-77 -- halves H and W and keeps every depth plane (any D; same parameter tree; eval only on the GPU)."""
 
     def __init__(self, in_chs: int, base_chs: int = 8, sample_stride: Tuple = (2, 2, 2), sample_padding: Tuple = (1, 1, 1)):
         super().__init__()
-        if tuple(sample_stride) != (2, 2, 2) or tuple(sample_padding) != (1, 1, 1):
-            raise NotImplementedError("conv kernels are built for sample_stride=(2,2,2), sample_padding=(1,1,1)")
+        if (tuple(sample_stride), tuple(sample_padding)) not in (((2, 2, 2), (1, 1, 1)), ((1, 2, 2), (0, 1, 1))):
+            raise NotImplementedError("conv kernels are built for sample_stride=(2,2,2), sample_padding=(1,1,1) and for the "
+                                      "depth-preserving sample_stride=(1,2,2), sample_padding=(0,1,1)")
+        self.sample_stride = tuple(sample_stride)
         a, b, c, d = base_chs, base_chs * 2, base_chs * 4, base_chs * 8
         self.conv01 = ConvBNReLU3D(in_chs, a)
         self.conv12 = nn.Sequential(ConvBNReLU3D(a, b, 3, sample_stride, 1), ConvBNReLU3D(b, b, 3, 1, 1))
@@ -129,6 +134,11 @@ class RegularNet_4Scales(nn.Module):
     fused_regress = True   # forward(cost, hypos) also returns the soft-argmin depth
 
     def forward(self, x: torch.Tensor, depth_hypos=None):
+        if self.sample_stride != (2, 2, 2) and layers.hip_train(self, x):
+            raise NotImplementedError(
+                f"RegularNet_4Scales(sample_stride={self.sample_stride}) has no GPU training path: the hand-written training kernels "
+                "(weight gradient with a separate depth stride, epilogue sums) are built for sample_stride=(2,2,2) only.  Train the "
+                "weights with the reference's trainer, or on the stock ops with rehearsal.enable(on_gpu=True), and evaluate them here")
         if layers.hip_train(self, x):
             # training on the GPU: every layer forward + backward on the hand-written kernels (mdfnet_hip/train_ops.py)
             from mdfnet_hip import train_ops

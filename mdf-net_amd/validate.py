@@ -30,6 +30,9 @@ def build_parser():
                         help="scale of the spread for a stage whose curve is atv (UCS-Net's lamb), each finite and > 0")
     parser.add_argument("--confidence", default="last", type=str, choices=list(config.CONFIDENCES),
                         help="which confidence map the confidence table is made of (eval.py --confidence)")
+    parser.add_argument("--regular_stride", default="2,2,2", type=str, choices=["2,2,2", "1,2,2"],
+                        help="sample stride of the stage-1/2 regularisers the checkpoint was trained with: 2,2,2 (the reference's composition) "
+                             "or 1,2,2 (its depth-preserving alternative: H and W are halved, every depth plane is kept)")
     parser.add_argument("--thresholds", default=None, type=str,
                         help="1 to 4 comma-separated error thresholds; default 2,4,8 (mm) for dtu, 1/256,1/128,1/64 of each item's depth "
                              "range for blendedmvs")
@@ -78,10 +81,11 @@ def main(argv=None):
     dataset = val_dataset(args.dataset, eval_args.nviews)
     curves, thresh = config.parse_pair(args.curves, str), config.parse_pair(args.prob_thresh, float)
     atv_scale = config.parse_pair(args.atv_scale, float)
+    regular_stride = config.parse_stride(args.regular_stride)
     default = args.aggregate == "vector" and curves == tuple(config.curve_calss[1:]) and thresh == tuple(config.prob_thresh[1:]) \
-        and args.confidence == "last"
+        and args.confidence == "last" and regular_stride == (2, 2, 2)
     model = config.model if default else config.build_model(aggregate=args.aggregate, curves=curves, prob_thresh=thresh, atv_scale=atv_scale,
-                                                            confidence=args.confidence)
+                                                            confidence=args.confidence, regular_stride=regular_stride)
     if args.pre_model is not None:
         model.load_state_dict(torch.load(args.pre_model, map_location="cpu")["model"])
     device = eval_args.DEVICE
