@@ -477,6 +477,38 @@ int mdf_view_scores(const double* rot, const double* trans, int n_img, const dou
                     double sigma1, double sigma2, void* workspace, long long ws_bytes, double* score, int* shared, int* status,
                     void* stream);
 
+/* ---- Scene import: undistorting a photograph to a pinhole camera, fp64 coordinates -------------------------------------------------
+ * What lets tools/colmap/main.py --undistort take a sparse model whose cameras are SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV or
+ * OPENCV_FISHEYE (COLMAP's documented models); the reference has no counterpart.  src [B][Hs][Ws][3], dst [B][Hd][Wd][3], valid
+ * [B][Hd][Wd] (or NULL): device, uint8, interleaved RGB.  coeffs: HOST, 12 doubles, copied into the kernel arguments.  The source
+ * camera is (fx, fy, cx, cy) with the distortion below, the output camera [[zoom fx scale, 0, cx scale], [0, zoom fy scale, cy scale]];
+ * pixel j covers [j, j + 1), its centre is j + 0.5.  No contraction, every product, sum and quotient rounded once, in this order:
+ *   sample (b, a) of output pixel (i, j), b outer, a, b = 0..nsub-1, n = nsub:
+ *                      X = (j + (a + 0.5) / n) / scale,  Y = (i + (b + 0.5) / n) / scale,
+ *                      x = (X - cx) / (zoom fx),  y = (Y - cy) / (zoom fy),  (xd, yd) = distort(x, y),
+ *                      U = ((fx xd) + cx) - 0.5,  V = ((fy yd) + cy) - 0.5.
+ *   distort, kind MDF_UNDISTORT_RATIONAL, coeffs = k1, k2, p1, p2, k3, k4, k5, k6, then four unused:
+ *                      xx = x x, yy = y y, r2 = xx + yy, r4 = r2 r2, r6 = r4 r2,
+ *                      rad = (((1 + k1 r2) + k2 r4) + k3 r6) / (((1 + k4 r2) + k5 r4) + k6 r6),  q = 2 (x y),
+ *                      xd = (x rad) + ((p1 q) + p2 (r2 + 2 xx)),  yd = (y rad) + ((p2 q) + p1 (r2 + 2 yy)).
+ *   distort, kind MDF_UNDISTORT_FISHEYE, coeffs = k1, k2, k3, k4, then eight unused:
+ *                      r = sqrt(r2); r = 0 gives (x, y); else t = atan(r), t2 = t t, t4 = t2 t2, t6 = t4 t2, t8 = t4 t4,
+ *                      sc = (t ((((1 + k1 t2) + k2 t4) + k3 t6) + k4 t8)) / r,  xd = x sc,  yd = y sc.
+ *   blank sample       U or V not finite, U < -0.5, U > Ws - 0.5, V < -0.5 or V > Hs - 0.5: it adds 0 to every channel.
+ *   any other sample   u = floor(U), wu = U - u, mu = 1 - wu (v, wv, mv alike), taps at columns max(u, 0), min(u + 1, Ws - 1) and
+ *                      rows max(v, 0), min(v + 1, Hs - 1); per channel top = (p00 mu) + p01 wu, bot = (p10 mu) + p11 wu,
+ *                      value = (top mv) + bot wv.
+ *   output             byte = floor(sum / (n n) + 0.5), the sum from 0 in (b, a) order; valid = 1 iff no sample of the pixel is blank.
+ * MDF_EARG: a null src, dst or coeffs, a size <= 0, nsub outside [1, 16], an unknown kind, a focal length, zoom or scale that is not
+ * finite and > 0, a coefficient or principal point that is not finite, B H W 3 > 2^31 - 1 for the source or the output.  Never
+ * allocates, never synchronises.                                                                                                  */
+#define MDF_UNDISTORT_RATIONAL 0
+#define MDF_UNDISTORT_FISHEYE 1
+#define MDF_UNDISTORT_MAX_NSUB 16
+int mdf_image_undistort(const uint8_t* src, uint8_t* dst, uint8_t* valid, int B, int Hs, int Ws, int Hd, int Wd, int kind,
+                        const double* coeffs, double fx, double fy, double cx, double cy, double zoom, double scale, int nsub,
+                        void* stream);
+
 /* =====================================================================================================
  * Training path (BASELINE config 3; train.py:36-45 -> loss.backward()).  The reference has no explicit backward:
  * autograd differentiates the op chains cited above.  Each entry below is the hand-written forward-in-train-mode or

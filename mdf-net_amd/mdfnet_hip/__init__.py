@@ -91,6 +91,7 @@ SIGNATURES = {
                                       c_fp, c_fp, c_fp, c_fp]),
     "mdf_view_scores": (c_int, [c_fp, c_fp, c_int, c_fp, c_i64, c_fp, c_fp, c_i64, c_i64] + [ctypes.c_double] * 3 + [c_fp, c_i64, c_fp,
                                 c_fp, c_fp, c_fp]),
+    "mdf_image_undistort": (c_int, [c_fp, c_fp, c_fp] + [c_int] * 6 + [ctypes.POINTER(ctypes.c_double)] + [ctypes.c_double] * 6 + [c_int, c_fp]),
     "mdf_bn_stats_fwd": (c_int, [c_fp, c_i64, c_int, c_int, c_fp, c_fp]),
     "mdf_bn_finalize_fwd": (c_int, [c_fp, c_fp, c_fp, ctypes.c_float, ctypes.c_float, c_i64, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_fp]),
     "mdf_bn_relu_apply_fwd": (c_int, [c_fp, c_fp, c_fp, c_fp, c_i64, c_int, c_int, c_fp]),

@@ -72,6 +72,8 @@ KERNEL_FAMILY = {
     "view_centre_kernel": POINT_EVAL, "view_track_kernel": POINT_EVAL, "view_fill_kernel": POINT_EVAL, "view_depth_key_kernel": POINT_EVAL,
     "view_regroup_kernel": POINT_EVAL, "view_range_kernel": POINT_EVAL, "view_expand_kernel": POINT_EVAL, "view_term_kernel": POINT_EVAL,
     "view_sum_kernel": POINT_EVAL,
+    # image_undistort.hip (scene import: a distorted photograph resampled to a pinhole camera)
+    "image_undistort_kernel": POINT_EVAL,
     # loss.hip
     "masked_smooth_l1_reduce_kernel": CONTROL, "masked_smooth_l1_finalize_kernel": CONTROL, "masked_smooth_l1_bwd_kernel": CONTROL,
     "masked_smooth_l1_reduce_multi_kernel": CONTROL, "masked_smooth_l1_bwd_multi_kernel": CONTROL, "adam_step_kernel": CONTROL,

@@ -1546,6 +1546,55 @@ def view_scores(rot, trans, pts, track_off, track_img, theta0=5.0, sigma1=1.0, s
     return res
 
 
+UNDISTORT_KINDS = {"rational": 0, "fisheye": 1}
+UNDISTORT_MAX_NSUB = 16
+
+
+def undistort_images(src, kind, coeffs, fx, fy, cx, cy, out_hw, zoom=1.0, scale=1.0, nsub=1, want_valid=False):
+    """Photographs of one distorted camera resampled to the pinhole camera [[zoom fx scale, 0, cx scale], [0, zoom fy scale, cy scale]]
+    (mdf_image_undistort; include/mdfnet_hip.h states the map, the bilinear taps and the nsub x nsub sample mean, all fp64).
+    src [B,H,W,3] uint8, contiguous, on the GPU; kind "rational" (coeffs k1, k2, p1, p2, k3, k4, k5, k6) or "fisheye" (k1..k4), coeffs up
+    to 12 values (the rest zero); out_hw = (Hd, Wd).  -> dst [B,Hd,Wd,3] uint8 (, valid [B,Hd,Wd] uint8: 1 where no sample of the
+    pixel fell outside the photograph), on the GPU."""
+    import math
+    import numpy as np
+    if not torch.is_tensor(src):
+        raise ValueError("undistort_images: src must be a tensor")
+    if not src.is_cuda:
+        raise ValueError("undistort_images: src must live on the GPU (there is no CPU fallback)")
+    if src.dtype != torch.uint8:
+        raise ValueError(f"undistort_images: src must be uint8, got {src.dtype}")
+    if src.dim() != 4 or src.shape[-1] != 3:
+        raise ValueError(f"undistort_images: src must be [B,H,W,3] (interleaved RGB), got {tuple(src.shape)}")
+    if not src.is_contiguous():
+        raise ValueError("undistort_images: src must be contiguous")
+    if kind not in UNDISTORT_KINDS:
+        raise ValueError(f"undistort_images: kind {kind!r} not in {sorted(UNDISTORT_KINDS)}")
+    c = np.asarray(coeffs, dtype=np.float64).reshape(-1)
+    if c.size > 12 or not np.isfinite(c).all():
+        raise ValueError(f"undistort_images: at most 12 finite coefficients, got {c.tolist()}")
+    c = np.concatenate([c, np.zeros(12 - c.size)])
+    b, hs, ws = (int(v) for v in src.shape[:3])
+    hd, wd = int(out_hw[0]), int(out_hw[1])
+    fx, fy, cx, cy, zoom, scale, nsub = float(fx), float(fy), float(cx), float(cy), float(zoom), float(scale), int(nsub)
+    if min(b, hs, ws, hd, wd) <= 0:
+        raise ValueError(f"undistort_images: empty sizes (source {tuple(src.shape)}, output {hd} x {wd})")
+    if 3 * b * max(hs * ws, hd * wd) > 2 ** 31 - 1:
+        raise ValueError(f"undistort_images: {b} images of {hs} x {ws} -> {hd} x {wd} exceed int32 indexing; pass fewer per call")
+    if not 1 <= nsub <= UNDISTORT_MAX_NSUB:
+        raise ValueError(f"undistort_images: nsub={nsub} out of range [1,{UNDISTORT_MAX_NSUB}]")
+    if not all(math.isfinite(v) and v > 0 for v in (fx, fy, zoom, scale)) or not (math.isfinite(cx) and math.isfinite(cy)):
+        raise ValueError(f"undistort_images: fx={fx}, fy={fy}, zoom={zoom}, scale={scale} must be finite and > 0, cx={cx}, cy={cy} finite")
+    dst = torch.empty((b, hd, wd, 3), device=src.device, dtype=torch.uint8)
+    valid = torch.empty((b, hd, wd), device=src.device, dtype=torch.uint8) if want_valid else None
+    d = ctypes.c_double
+    _abi("mdf_image_undistort", (src.data_ptr(), dst.data_ptr(), valid.data_ptr() if want_valid else None, b, hs, ws, hd, wd,
+                                 UNDISTORT_KINDS[kind], _host_doubles(c, 12), d(fx), d(fy), d(cx), d(cy), d(zoom), d(scale), nsub,
+                                 _stream(src)), tag=f"b{b} {ws}x{hs}->{wd}x{hd} n{nsub} {kind}",
+         work={"points": float(b * hd * wd * nsub * nsub), "bound": "hbm"})
+    return (dst, valid) if want_valid else dst
+
+
 def icp_sums(src, tgt, nearest, d2, threshold):
     """The sums of one point-to-point ICP step (mdf_pts_icp_sums) over the pairs (src[i], tgt[nearest[i]]) with nearest[i] >= 0 and
     sqrt(d2[i]) < threshold -> host numpy [17]: inlier count, sum of d^2, source centroid, target centroid, H (3x3 row-major,

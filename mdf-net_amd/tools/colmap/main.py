@@ -1,10 +1,13 @@
 """Scene import: a folder of images plus a COLMAP sparse model -> the scene layout eval.py -d scene reads.
 
   python mdf-net_amd/tools/colmap/main.py --model SPARSE_DIR --images IMAGE_DIR --out ROOT/SCENE [--nsrc 10]
-         [--theta0 5 --sigma1 1 --sigma2 10] [--quantiles 0.01,0.99] [--max_dim 0]
+         [--theta0 5 --sigma1 1 --sigma2 10] [--quantiles 0.01,0.99] [--max_dim 0] [--undistort [--undistort_fit inside|same]]
 
-The model (text or binary; PINHOLE / SIMPLE_PINHOLE cameras, so undistort first) gives the cameras, the sparse points and their
-tracks.  On the GPU (ops.view_scores, ops.view_depth_ranges) every image pair is scored by the triangulation
+The model (text or binary) gives the cameras, the sparse points and their tracks.  Its cameras are PINHOLE / SIMPLE_PINHOLE; with
+--undistort also SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV and OPENCV_FISHEYE, whose images are resampled to a pinhole camera on
+the GPU (ops.undistort_images, tools/colmap/undistort.py) and whose cam files carry that camera: zoomed until no border pixel falls
+outside the photograph (--undistort_fit inside, the default) or at the photograph's own focal length, black where it has nothing
+(same).  Without the flag such a model is refused with the advice to undistort first.  On the GPU (ops.view_scores, ops.view_depth_ranges) every image pair is scored by the triangulation
 angles of the points it shares and every image gets the depth range its own observations span; the host picks the --nsrc best
 sources per image.  Written under --out:
   images/%08d.jpg    ids dense 0..N-1 in ascending COLMAP image id.  --max_dim D scales an image whose longer side exceeds D down
@@ -28,7 +31,7 @@ import shutil  # noqa: E402
 
 import numpy as np  # noqa: E402
 
-from tools.colmap import model_io  # noqa: E402
+from tools.colmap import model_io, undistort as undist  # noqa: E402
 from tools.colmap.select import select_views  # noqa: E402
 
 MULTIPLE = 32
@@ -74,11 +77,15 @@ def export_image(src, dst, K, max_dim=0):
 
 
 def import_scene(model_dir, image_dir, out_dir, nsrc=10, theta0=5.0, sigma1=1.0, sigma2=10.0, quantiles=(0.01, 0.99), max_dim=0,
-                 device=None, log=print):
-    """-> dict with score [N,N], shared [N,N], range [N,2], count [N], sources [N,k] (numpy) and the scene arrays."""
+                 device=None, log=print, undistort=False, undistort_fit="inside"):
+    """-> dict with score [N,N], shared [N,N], range [N,2], count [N], sources [N,k] (numpy) and the scene arrays.  undistort: read
+    the distorted camera models too and resample their images (tools/colmap/undistort.py); a pinhole camera's images are exported
+    as without it."""
     import torch
     from mdfnet_hip import ops
-    scene = model_io.scene_arrays(model_io.read_model(model_dir), log=log)
+    if undistort_fit not in undist.FITS:
+        raise SystemExit(f"--undistort_fit {undistort_fit!r}: one of {', '.join(undist.FITS)}")
+    scene = model_io.scene_arrays(model_io.read_model(model_dir, distorted=undistort), log=log)
     n = len(scene["names"])
     if n == 0:
         raise SystemExit(f"{model_dir}: no image with observations")
@@ -90,12 +97,23 @@ def import_scene(model_dir, image_dir, out_dir, nsrc=10, theta0=5.0, sigma1=1.0,
     sources = select_views(score, nsrc)
     for sub in ("images", "cams"):
         os.makedirs(os.path.join(out_dir, sub), exist_ok=True)
+    paths = [os.path.join(image_dir, name) for name in scene["names"]]
+    for i, src in enumerate(paths):
+        if not os.path.exists(src):
+            raise SystemExit(f"{src}: the image of COLMAP image {int(scene['colmap_ids'][i])} is missing")
+    written_K = {}                                          # image -> K_out, for the images of distorted cameras
+    for cam_id in sorted(set(int(c) for c in scene["camera_ids"])):          # one plan (and one zoom fit) per camera
+        members = [i for i in range(n) if int(scene["camera_ids"][i]) == cam_id]
+        camera = scene["cameras"][members[0]]
+        if camera[0] in model_io.SUPPORTED_MODELS:
+            continue
+        what = f"camera {cam_id} ({camera[0]})"
+        p = undist.plan(camera, max_dim, undistort_fit, what)
+        undist.export_images([(paths[i], os.path.join(out_dir, "images", "%08d.jpg" % i)) for i in members], p, device, what, log)
+        written_K.update((i, p["K_out"]) for i in members)
     with open(os.path.join(out_dir, "index.txt"), "w") as index:
         for i in range(n):
-            src = os.path.join(image_dir, scene["names"][i])
-            if not os.path.exists(src):
-                raise SystemExit(f"{src}: the image of COLMAP image {int(scene['colmap_ids'][i])} is missing")
-            K, _ = export_image(src, os.path.join(out_dir, "images", "%08d.jpg" % i), scene["K"][i], max_dim)
+            K = written_K[i] if i in written_K else export_image(paths[i], os.path.join(out_dir, "images", "%08d.jpg" % i), scene["K"][i], max_dim)[0]
             if not rng[i, 0] > 0:
                 log(f"image {i}: depth range starts at {rng[i, 0]!r}; points behind the camera?")
             write_cam(os.path.join(out_dir, "cams", "%08d_cam.txt" % i), scene["rot"][i], scene["trans"][i], K, rng[i, 0], rng[i, 1])
@@ -105,7 +123,7 @@ def import_scene(model_dir, image_dir, out_dir, nsrc=10, theta0=5.0, sigma1=1.0,
     return dict(scene, score=score, shared=shared, range=rng, count=count, sources=sources)
 
 
-def main():
+def build_parser():
     parser = argparse.ArgumentParser(description="import a scene from a COLMAP sparse model")
     parser.add_argument("--model", required=True, type=str, help="folder with cameras/images/points3D .txt or .bin")
     parser.add_argument("--images", required=True, type=str, help="folder the model's image names are relative to")
@@ -116,11 +134,20 @@ def main():
     parser.add_argument("--sigma2", default=10.0, type=float)
     parser.add_argument("--quantiles", default="0.01,0.99", type=str)
     parser.add_argument("--max_dim", default=0, type=int)
-    args = parser.parse_args()
+    parser.add_argument("--undistort", action="store_true", help="read SIMPLE_RADIAL / RADIAL / OPENCV / FULL_OPENCV / OPENCV_FISHEYE "
+                        "cameras too and resample their images to a pinhole camera on the GPU")
+    parser.add_argument("--undistort_fit", default="inside", choices=undist.FITS, help="inside: zoom until no border pixel falls outside "
+                        "the photograph; same: keep the focal length, pixels the photograph does not cover stay black")
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     q = tuple(float(x) for x in args.quantiles.split(","))
     if len(q) != 2:
         raise SystemExit(f"--quantiles {args.quantiles!r}: two comma-separated values")
-    import_scene(args.model, args.images, args.out, args.nsrc, args.theta0, args.sigma1, args.sigma2, q, args.max_dim)
+    import_scene(args.model, args.images, args.out, args.nsrc, args.theta0, args.sigma1, args.sigma2, q, args.max_dim,
+                 undistort=args.undistort, undistort_fit=args.undistort_fit)
 
 
 if __name__ == "__main__":

@@ -11,6 +11,9 @@ CAMERA_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL
                  5: ("OPENCV_FISHEYE", 8), 6: ("FULL_OPENCV", 12), 7: ("FOV", 5), 8: ("SIMPLE_RADIAL_FISHEYE", 4),
                  9: ("RADIAL_FISHEYE", 5), 10: ("THIN_PRISM_FISHEYE", 12)}
 SUPPORTED_MODELS = ("PINHOLE", "SIMPLE_PINHOLE")
+# read with distorted=True besides those two (main.py --undistort resamples their images on the GPU: tools/colmap/undistort.py)
+DISTORTED_MODELS = ("SIMPLE_RADIAL", "RADIAL", "OPENCV", "FULL_OPENCV", "OPENCV_FISHEYE")
+ONE_FOCAL_MODELS = ("SIMPLE_PINHOLE", "SIMPLE_RADIAL", "RADIAL")
 
 
 def _data_lines(path):
@@ -71,16 +74,23 @@ def _read_binary(folder):
     return cameras, images, points
 
 
-def read_model(folder):
+def read_model(folder, distorted=False):
     """-> dict of arrays, images in ascending COLMAP image id and points in ascending point id:
     camera_models {camera id: (model name, width, height, params)}, image_ids [N] int64, qvec [N,4], tvec [N,3] float64,
     camera_ids [N] int64, names (list), point_ids [P] int64, xyz [P,3] float64, track_off [P+1] int64, track_image_ids [T] int64
-    (COLMAP image ids, in file order).  The binary files are used when cameras.bin exists, else the text files."""
+    (COLMAP image ids, in file order).  The binary files are used when cameras.bin exists, else the text files.  A camera that is not
+    PINHOLE or SIMPLE_PINHOLE exits with the advice; with distorted=True the DISTORTED_MODELS are read as well."""
     cameras, images, points = _read_binary(folder) if os.path.exists(os.path.join(folder, "cameras.bin")) else _read_text(folder)
-    for cam_id, (name, _, _, _) in sorted(cameras.items()):
-        if name not in SUPPORTED_MODELS:
+    for cam_id, (name, _, _, params) in sorted(cameras.items()):
+        if distorted and name not in SUPPORTED_MODELS + DISTORTED_MODELS:
+            raise SystemExit(f"camera {cam_id} has model {name}: --undistort reads {', '.join(SUPPORTED_MODELS + DISTORTED_MODELS)}. "
+                             "Undistort the images first (colmap image_undistorter) and import the undistorted sparse model")
+        if not distorted and name not in SUPPORTED_MODELS:
             raise SystemExit(f"camera {cam_id} has model {name}: only {' and '.join(SUPPORTED_MODELS)} are read. Undistort the images first "
-                             "(colmap image_undistorter) and import the undistorted sparse model")
+                             "(colmap image_undistorter) and import the undistorted sparse model, or pass --undistort")
+        want = next(k for n, k in CAMERA_MODELS.values() if n == name)
+        if len(params) != want:
+            raise SystemExit(f"camera {cam_id} ({name}) has {len(params)} parameters, {want} expected")
     images.sort(key=lambda r: r[0])
     points.sort(key=lambda r: r[0])
     lens = np.array([len(p[2]) for p in points], dtype=np.int64)
@@ -106,10 +116,33 @@ def quaternion_to_rotation(q):
 
 
 def intrinsics(camera):
-    """(model, width, height, params) -> K [3,3] float64."""
+    """(model, width, height, params) -> K [3,3] float64 (f on both axes for a model with one focal length)."""
     name, _, _, p = camera
-    fx, fy, cx, cy = (p[0], p[0], p[1], p[2]) if name == "SIMPLE_PINHOLE" else (p[0], p[1], p[2], p[3])
+    fx, fy, cx, cy = (p[0], p[0], p[1], p[2]) if name in ONE_FOCAL_MODELS else (p[0], p[1], p[2], p[3])
     return np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], dtype=np.float64)
+
+
+def distortion(camera):
+    """(model, width, height, params) -> (kind, coeffs [12] float64), the arguments of ops.undistort_images: kind "rational" with
+    k1, k2, p1, p2, k3, k4, k5, k6 (SIMPLE_RADIAL, RADIAL, OPENCV and the pinhole models are special cases with zeros) or "fisheye"
+    with k1..k4 (OPENCV_FISHEYE); the rest of coeffs is zero."""
+    name, _, _, p = camera
+    p = np.asarray(p, dtype=np.float64)
+    c = np.zeros(12, dtype=np.float64)
+    if name == "OPENCV_FISHEYE":
+        c[:4] = p[4:8]
+        return "fisheye", c
+    if name == "SIMPLE_RADIAL":
+        c[0] = p[3]
+    elif name == "RADIAL":
+        c[:2] = p[3:5]
+    elif name == "OPENCV":
+        c[:4] = p[4:8]
+    elif name == "FULL_OPENCV":
+        c[:8] = p[4:12]
+    elif name not in SUPPORTED_MODELS:
+        raise SystemExit(f"camera model {name}: no distortion model here ({', '.join(SUPPORTED_MODELS + DISTORTED_MODELS)})")
+    return "rational", c
 
 
 def tracks_csr(point_index, image_index, n_pts):
@@ -125,7 +158,7 @@ def scene_arrays(model, log=print):
     of images the model does not list are dropped, an image without observations is left out (one line each), and the remaining
     images get dense ids 0..N-1 in ascending COLMAP id.
     -> dict: rot [N,3,3], trans [N,3], K [N,3,3], size [N,2] (width, height), colmap_ids [N], names, pts [P,3], track_off [P+1]
-    int64, track_img [T] int32."""
+    int64, track_img [T] int32, camera_ids [N] (COLMAP camera id per image), cameras (per image its (model, width, height, params))."""
     finite = np.isfinite(model["xyz"]).all(axis=1)
     if not finite.all():
         log(f"dropped {int((~finite).sum())} of {len(finite)} points with non-finite coordinates")
@@ -148,4 +181,5 @@ def scene_arrays(model, log=print):
             "K": np.stack([intrinsics(c) for c in cams]) if cams else np.zeros((0, 3, 3)),
             "size": np.array([[c[1], c[2]] for c in cams], dtype=np.int64).reshape(-1, 2),
             "colmap_ids": ids[keep], "names": [model["names"][i] for i in keep],
+            "camera_ids": model["camera_ids"][keep], "cameras": cams,
             "pts": np.ascontiguousarray(model["xyz"][finite]), "track_off": off, "track_img": img}
