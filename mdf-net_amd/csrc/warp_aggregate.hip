@@ -630,7 +630,7 @@ extern "C" int mdf_homo_warp_fwd(const float* src_fea, int fea_layout, const flo
 extern "C" int mdf_warp_corner_indices(const float* proj, const float* hypos, int hypos_per_pixel, int32_t* x0y0,
                                        int B, int D, int h, int w, void* stream) {
   MDF_REQUIRE(proj && hypos && x0y0, "null pointer argument");
-  MDF_REQUIRE(B > 0 && D > 0 && h > 1 && w > 1, "bad shape");
+  MDF_REQUIRE(B > 0 && D > 0 && h > 1 && w > 1, "bad shape B=%d D=%d h=%d w=%d", B, D, h, w);
   const size_t n = (size_t)B * D * h * w;
   const int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
   hipLaunchKernelGGL(corner_index_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, proj, hypos, hypos_per_pixel,
