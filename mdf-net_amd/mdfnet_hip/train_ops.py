@@ -331,11 +331,28 @@ def dgrad_pack(conv, transposed):
     return cache_of_key(conv, "dgrad").get((w,), build)
 
 
-def conv3d_dgrad(conv, transposed, dy, add_to=None, stat=None):
+def _refuse_odd_extents(what, got, in_shape):
+    """A stride-2 layer's input gradient runs on the transposed kernel, whose output is twice dy's extent on every axis: the gradient of
+    an input with EVEN extents.  For an odd extent 2 * out = in + 1: the last plane, row or column would be the gradient of the zero
+    padding.  dy alone does not tell the parity of the input's extents, so a stride-2 layer's caller has to name its input's shape,
+    and a shape the gradient would not have is refused instead of handed over as a tensor of another shape."""
+    if in_shape is None:
+        raise ValueError(f"{what}: the input gradient of a stride-2 layer needs in_shape, the shape of the layer's input")
+    if tuple(got) != tuple(in_shape):
+        raise ValueError(f"{what}: the input gradient of a stride-2 layer covers {tuple(got)}, the input is {tuple(in_shape)}: "
+                         "odd input extents are not supported")
+
+
+def conv3d_dgrad(conv, transposed, dy, add_to=None, stat=None, in_shape=None):
     """dx = [add_to +] (input gradient of the layer) as one launch of the forward conv kernel family.  stat = (y_p, aux_p, red):
     dx is the complete dz of the layer that produced this layer's input (raw conv output y_p, BatchNorm constants aux_p) --
-    its BatchNorm-backward sums are accumulated into `red` by the launch's epilogue."""
+    its BatchNorm-backward sums are accumulated into `red` by the launch's epilogue.
+    in_shape: the input's [B, D, H, W, Cin], required for a stride-2 Conv3d.  Its dx is [B, 2Do, 2Ho, 2Wo, Cin] for dy [B, Do, Ho, Wo,
+    Cout], the input's shape where its extents are even; an odd extent (one plane / row / column less than that) is refused with a
+    ValueError before anything is launched."""
     wp = dgrad_pack(conv, transposed)
+    if not transposed and conv.stride[0] == 2:
+        _refuse_odd_extents("conv3d_dgrad", (dy.shape[0], 2 * dy.shape[1], 2 * dy.shape[2], 2 * dy.shape[3], conv.in_channels), in_shape)
     if transposed:        # backward of ConvTranspose3d(Cin->Cout): stride-2 conv Cout -> Cin
         stride, tr = 2, False
     elif conv.stride[0] == 2:
@@ -437,7 +454,7 @@ class Tape:
                 pl = self.layers[prod]
                 stat = (pl[5], pl[6], pool.take(ops.STAT_SLICES * 2 * pl[0].out_channels))
                 red_of[prod] = stat[2]
-            grads[id(x)] = conv3d_dgrad(conv, tr, dy, add_to=grads.get(id(x)), stat=stat)
+            grads[id(x)] = conv3d_dgrad(conv, tr, dy, add_to=grads.get(id(x)), stat=stat, in_shape=x.shape)
         return pg
 
 
@@ -729,10 +746,14 @@ def _dgrad2d_pack(conv):
     raise NotImplementedError(f"conv2d input gradient for k={k} stride={stride}")
 
 
-def conv2d_dgrad(conv, dy, stat=None, groups=1):
+def conv2d_dgrad(conv, dy, stat=None, groups=1, in_shape=None):
     """Input gradient of a Conv2d(k3,s1,p1) or Conv2d(k5,s2,p2) layer, NHWC, on the forward conv kernels.  stat = (y_p, aux_p, red)
-    (k3 only): the BatchNorm-backward sums of the producing layer ride in the launch's epilogue, as in conv3d_dgrad."""
+    (k3 only): the BatchNorm-backward sums of the producing layer ride in the launch's epilogue, as in conv3d_dgrad.
+    k5 s2: in_shape, the input's [B, H, W, Cin], is required; dx is [B, 2Ho, 2Wo, Cin], the input's shape where H and W are even, and
+    an odd H or W is refused with a ValueError, as in conv3d_dgrad."""
     k, cin, cout = conv.kernel_size[0], conv.in_channels, conv.out_channels
+    if k == 5:
+        _refuse_odd_extents("conv2d_dgrad", (dy.shape[0], 2 * dy.shape[1], 2 * dy.shape[2], cin), in_shape)
     packs = _dgrad2d_pack(conv)
     if k == 3:
         if stat is not None:
@@ -796,7 +817,7 @@ class Tape2D:
                     pl = self.layers[prod]
                     stat = (pl[3], pl[4], pool.take(ops.STAT_SLICES * self.groups * 2 * pl[0].out_channels))
                     red_of[prod] = stat[2]
-                dx = conv2d_dgrad(conv, dy, stat=stat, groups=self.groups)
+                dx = conv2d_dgrad(conv, dy, stat=stat, groups=self.groups, in_shape=x.shape)
                 grads[id(x)] = dx if id(x) not in grads else grads[id(x)] + dx
         return pg
 

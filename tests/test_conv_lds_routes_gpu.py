@@ -183,7 +183,7 @@ def run3d(cin, cout, shape, variant):
     return T.train(cin, cout, "s1", shape, int(variant[2]), variant == "st2")
 
 
-def run2d(cin, cout, k, stride, shape, variant):
+def run2d(cin, cout, k, stride, shape, variant, res_scale=0.1):
     from mdfnet_hip import ops
     x, wp, alpha, beta, res, res_up, stat_y, aux = layer2d(cin, cout, k, stride, shape)
     planar = cin < 4 and variant != "nhwc"
@@ -195,7 +195,7 @@ def run2d(cin, cout, k, stride, shape, variant):
         return ops.conv2d_train(x, wp, cin, cout, k, stride, planar, mode, sums, groups, stat_y if mode == 2 else None,
                                 aux[:groups * 4 * cout] if mode == 2 else None)
     if variant == "epi":
-        return ops.conv2d_nhwc(x, wp, cin, cout, k, stride, alpha, beta, True, res, 0.1, planar_in=planar)
+        return ops.conv2d_nhwc(x, wp, cin, cout, k, stride, alpha, beta, True, res, res_scale, planar_in=planar)
     if variant == "resup":
         return ops.conv2d_nhwc(x, wp, cin, cout, k, stride, alpha, beta, False, res_up=res_up, planar_in=planar)
     return ops.conv2d_nhwc(x, wp, cin, cout, k, stride, planar_in=planar, pixel_shuffle2=(variant == "shuf"))

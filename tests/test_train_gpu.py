@@ -82,10 +82,10 @@ def test_conv3d_input_and_weight_gradients(cin, cout, stride, tr):
     convd = conv.to(DEV)
     xd = ops.to_ndhwc(x.detach().to(DEV))
     dyd = ops.to_ndhwc(dy.to(DEV))
-    dx = train_ops.conv3d_dgrad(convd, tr, dyd)
+    dx = train_ops.conv3d_dgrad(convd, tr, dyd, in_shape=xd.shape)
     assert _rel(ops.from_ndhwc(dx), x.grad) < 2e-5
     extra = torch.randn_like(dx)
-    dx2 = train_ops.conv3d_dgrad(convd, tr, dyd, add_to=extra)          # fused accumulation into a skip gradient
+    dx2 = train_ops.conv3d_dgrad(convd, tr, dyd, add_to=extra, in_shape=xd.shape)          # fused accumulation into a skip gradient
     assert _rel(dx2, dx + extra) < 1e-5
     dw = train_ops.conv3d_wgrad(xd, dyd, 2, tuple(conv.weight.shape)) if tr else train_ops.conv3d_wgrad(dyd, xd, stride, tuple(conv.weight.shape))
     assert _rel(dw, conv.weight.grad.cpu()) < 3e-5
@@ -845,7 +845,7 @@ def test_conv2d_input_and_weight_gradients(cin, cout, k, stride):
     else:
         xd = ops.to_nhwc(x.detach().to(DEV))
         dw = train_ops.conv2d_wgrad(dyd, xd, k, stride, tuple(conv.weight.shape))
-        dx = train_ops.conv2d_dgrad(convd, dyd)
+        dx = train_ops.conv2d_dgrad(convd, dyd, in_shape=xd.shape)
         assert _rel(ops.from_nhwc(dx), x.grad) < 2e-5
     assert _rel(dw, conv.weight.grad.cpu()) < 3e-5
 
