@@ -769,6 +769,40 @@ int mdf_adam_step_hyper(const void* jobs_dev, const int* block_job_dev, int nblo
                         float* exp_avg_sq, const float* hyper_dev, float beta1, float beta2, float eps, float weight_decay,
                         void* stream);
 
+/* ---- meshing (no counterpart in the reference: it stops at a point cloud; DESIGN section 7 "TSDF meshing").
+ *      Volume: dims = (nx, ny, nz) lattice points, x fastest; point (i,j,k) sits at origin + voxel * (i,j,k).  dims and origin are
+ *      HOST arrays of 3.  D, W [nz][ny][nx] float: the truncated signed distance (in units of trunc, <= 1) and the observation count.
+ *      Views: depths (and images) are HOST arrays of nviews DEVICE pointers to [h][w] float maps ([h][w][3] uint8 images); cams is a
+ *      HOST table [nviews][MDF_TSDF_CAM_FLOATS] float: R row-major [0..8], t [9..11] (p_cam = R x + t, the rows of the extrinsic),
+ *      fx, fy, cx, cy [12..15] (no skew), [16] the largest finite positive texel of the view's depth map (-inf if it has none; read
+ *      by mdf_tsdf_integrate only), rest 0.  A point projects to the texel (floor(fx x/z + cx + 0.5), floor(fy y/z + cy + 0.5)).
+ *
+ *   mdf_tsdf_integrate  every lattice point walks the views in the order given: skip if z <= 0 or not finite, if the texel is off
+ *                       the map, if its depth d is not finite or <= 0, if d - z < -trunc; else f = min(1, (d - z) / trunc),
+ *                       D <- (D W + f) / (W + 1), W <- W + 1.  `chunk` views per launch (0 = MDF_TSDF_CHUNK, the largest); the
+ *                       result does not depend on it, nor on MDF_TSDF_CULL=0 (no brick of points skips a view as a whole).
+ *   mdf_mesh_count      marching tetrahedra over the Kuhn split of every cell whose 8 corners have W >= min_weight; a corner is
+ *                       inside if D < 0.  Leaves totals[0] = vertices, totals[1] = triangles (DEVICE, int64) and, in the
+ *                       workspace (>= MDF_MESH_WORKSPACE_BYTES(nx ny nz) bytes, 16-byte aligned), what mdf_mesh_emit needs.
+ *   mdf_mesh_emit       with the same volume, min_weight and workspace: vertices [n_vertices][3] float in increasing (lattice
+ *                       index, edge direction), triangles [n_triangles][3] int32 in increasing (cell, tetrahedron, triangle),
+ *                       normals towards D > 0.  Not to be called for an empty mesh; a total >= 2^31 is MDF_EUNSUPPORTED.
+ *   mdf_mesh_colour     per vertex, over the views that see it with |d - z| <= trunc: the mean of the nearest texels of the images,
+ *                       rounded half up; (128,128,128) where no view does.  acc: [n][4] float scratch, 16-byte aligned.            */
+#define MDF_TSDF_CHUNK 16
+#define MDF_TSDF_CAM_FLOATS 20
+#define MDF_MESH_CHUNK 1024
+#define MDF_MESH_WORKSPACE_BYTES(n) (18ll * (n) + 24ll * (((n) + MDF_MESH_CHUNK - 1) / MDF_MESH_CHUNK) + 256)
+int mdf_tsdf_integrate(float* D, float* W, const int* dims, const float* origin, float voxel, float trunc,
+                       const float* const* depths, const float* cams, int nviews, int h, int w, int chunk, void* stream);
+int mdf_mesh_count(const float* D, const float* W, const int* dims, const float* origin, float voxel, float min_weight,
+                   void* workspace, long long workspace_bytes, long long* totals, void* stream);
+int mdf_mesh_emit(const float* D, const float* W, const int* dims, const float* origin, float voxel, float min_weight,
+                  void* workspace, long long workspace_bytes, long long n_vertices, long long n_triangles, float* vertices,
+                  int* triangles, void* stream);
+int mdf_mesh_colour(const float* vertices, long long n, const float* const* depths, const unsigned char* const* images,
+                    const float* cams, int nviews, int h, int w, float trunc, float* acc, unsigned char* rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

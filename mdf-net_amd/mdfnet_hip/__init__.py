@@ -145,6 +145,10 @@ SIGNATURES = {
     "mdf_hypos_from_fit_fwd": (c_int, [c_int, c_fp, c_fp, c_fp, ctypes.c_float, c_fp] + [c_int] * 5 + [c_fp]),
     "mdf_atv_spread_fwd": (c_int, [c_fp, c_fp, c_fp, c_int, ctypes.c_float, c_fp] + [c_int] * 4 + [c_fp]),
     "mdf_atv_hypos_fwd": (c_int, [c_fp, c_fp, c_fp] + [c_int] * 5 + [c_fp]),
+    "mdf_tsdf_integrate": (c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_float, ctypes.c_float, ctypes.POINTER(c_fp), c_fp] + [c_int] * 4 + [c_fp]),
+    "mdf_mesh_count": (c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_float, ctypes.c_float, c_fp, c_i64, c_fp, c_fp]),
+    "mdf_mesh_emit": (c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_float, ctypes.c_float, c_fp, c_i64, c_i64, c_i64, c_fp, c_fp, c_fp]),
+    "mdf_mesh_colour": (c_int, [c_fp, c_i64, ctypes.POINTER(c_fp), ctypes.POINTER(c_fp), c_fp] + [c_int] * 3 + [ctypes.c_float, c_fp, c_fp, c_fp]),
 }
 
 

@@ -18,6 +18,7 @@ PROB = "prob_head"
 HEADS = "heads"
 FILTER = "consistency_filter"
 POINT_EVAL = "point_eval"                  # DTU point-cloud evaluation: spatial index, nearest-neighbour distances, reduction, masks
+MESH = "mesh"                              # TSDF fusion of depth maps, marching tetrahedra, vertex colour (tools/mesh)
 CONTROL = "control"                        # weight packing, Adam, loss, finalisers: launch-bound one-block kernels
 
 KERNEL_FAMILY = {
@@ -74,6 +75,8 @@ KERNEL_FAMILY = {
     "view_sum_kernel": POINT_EVAL,
     # image_undistort.hip (scene import: a distorted photograph resampled to a pinhole camera)
     "image_undistort_kernel": POINT_EVAL,
+    # tsdf_mesh.hip (meshing: TSDF integration, marching tetrahedra over the Kuhn split, vertex colour)
+    "tsdf_integrate_kernel": MESH, "mesh_count_kernel": MESH, "mesh_scan_kernel": MESH, "mesh_emit_kernel": MESH, "mesh_colour_kernel": MESH,
     # loss.hip
     "masked_smooth_l1_reduce_kernel": CONTROL, "masked_smooth_l1_finalize_kernel": CONTROL, "masked_smooth_l1_bwd_kernel": CONTROL,
     "masked_smooth_l1_reduce_multi_kernel": CONTROL, "masked_smooth_l1_bwd_multi_kernel": CONTROL, "adam_step_kernel": CONTROL,

@@ -1760,3 +1760,142 @@ def tanks_eval_scene(est, gt, crop, tau, init, device=None):
                stage_rmse=np.array(stage_r), stage_iterations=np.array(stage_i, dtype=np.int64), hist_est=h1, hist_gt=h2,
                hist_edges=edges, dist_est=d1, dist_gt=d2)
     return res
+
+
+# --------------------------------------------------------------------------- meshing: TSDF fusion, marching tetrahedra, vertex colour
+TSDF_CHUNK = 16                # MDF_TSDF_CHUNK: views per launch
+TSDF_CAM_FLOATS = 20           # MDF_TSDF_CAM_FLOATS
+MESH_CHUNK = 1024              # MDF_MESH_CHUNK
+
+
+def tsdf_cameras(K, E, dmax=None):
+    """HOST: the camera table of mdf_tsdf_integrate / mdf_mesh_colour from intrinsics K [V,3,3] and extrinsics E [V,4,4] (any
+    array-like), rounded to fp32: R row-major, t, fx, fy, cx, cy (no skew), dmax (the largest valid depth of the view's map)."""
+    import numpy as np
+    K = np.asarray(torch.as_tensor(K).detach().cpu().numpy(), dtype=np.float32).reshape(-1, 3, 3)
+    E = np.asarray(torch.as_tensor(E).detach().cpu().numpy(), dtype=np.float32).reshape(-1, 4, 4)
+    if len(K) != len(E):
+        raise ValueError(f"{len(K)} intrinsics for {len(E)} extrinsics")
+    t = np.zeros((len(K), TSDF_CAM_FLOATS), np.float32)
+    t[:, 0:9] = E[:, :3, :3].reshape(-1, 9)
+    t[:, 9:12] = E[:, :3, 3]
+    t[:, 12], t[:, 13], t[:, 14], t[:, 15] = K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]
+    if dmax is not None:
+        t[:, 16] = np.asarray(dmax, np.float32)
+    return np.ascontiguousarray(t)
+
+
+def _tsdf_views(depths, what="depths", dtype=torch.float32, tail=()):
+    """[V,h,w(,3)] tensor or list of V same-shaped maps -> list of contiguous maps of `dtype` (no copy when already so)."""
+    maps = list(depths) if not torch.is_tensor(depths) else [depths[v] for v in range(depths.shape[0])]
+    if not maps:
+        raise ValueError(f"{what}: at least one view is needed")
+    _need_gpu(*maps)
+    shape = tuple(maps[0].shape)
+    if len(shape) != 2 + len(tail) or shape[2:] != tuple(tail) or any(tuple(m.shape) != shape for m in maps):
+        raise ValueError(f"{what}: every view needs the same [h,w{',3' if tail else ''}] shape, got {[tuple(m.shape) for m in maps][:4]}")
+    return [m if (m.dtype == dtype and m.is_contiguous()) else m.to(dtype).contiguous() for m in maps]
+
+
+def _volume_args(origin, voxel, dims):
+    import numpy as np
+    dims = tuple(int(d) for d in dims)
+    if len(dims) != 3:
+        raise ValueError(f"dims={dims}: (nx, ny, nz) is expected")
+    o = (ctypes.c_float * 3)(*[float(x) for x in np.asarray(torch.as_tensor(origin).cpu().numpy(), np.float32).reshape(3)])
+    return (ctypes.c_int * 3)(*dims), o, ctypes.c_float(float(np.float32(voxel))), dims
+
+
+def tsdf_integrate(depths, K, E, origin, voxel, dims, trunc, state=None, chunk=None):
+    """Integrate V depth maps ([V,h,w] GPU tensor or list of [h,w]; 0 / non-finite = no depth) into a truncated signed distance
+    volume of dims = (nx, ny, nz) lattice points at origin + voxel * (i,j,k); trunc in world units.  -> (D, W) [nz,ny,nx] fp32:
+    every point's running mean of min(1, (d - z) / trunc) over the views that see it, in the order given, and their number.
+    state = (D, W) continues an earlier call (the tensors are updated in place and returned); chunk = views per launch
+    (<= TSDF_CHUNK, the default).  The result does not depend on chunk or on where a sequence of calls was split."""
+    import numpy as np
+    maps = _tsdf_views(depths)
+    h, w = maps[0].shape
+    cdims, corigin, cvoxel, dims = _volume_args(origin, voxel, dims)
+    dev = maps[0].device
+    if state is None:
+        D = torch.zeros((dims[2], dims[1], dims[0]), device=dev, dtype=torch.float32) if min(dims) > 0 else None
+        W = torch.zeros_like(D) if D is not None else None
+    else:
+        D, W = state
+        _need_gpu(D, W)
+        if tuple(D.shape) != dims[::-1] or tuple(W.shape) != dims[::-1] or D.dtype != torch.float32 or W.dtype != torch.float32 \
+                or not D.is_contiguous() or not W.is_contiguous():
+            raise ValueError(f"state: two contiguous fp32 tensors of shape {dims[::-1]} are expected")
+    # the largest valid depth of every view, for the brick culling (torch.aminmax over the map with invalid texels at -inf)
+    stack = torch.stack(maps).flatten(1)
+    valid = torch.isfinite(stack) & (stack > 0)
+    dmax = torch.aminmax(torch.where(valid, stack, torch.full_like(stack, float("-inf"))), dim=1).max.cpu().numpy()
+    cams = tsdf_cameras(K, E, dmax)
+    if len(cams) != len(maps):
+        raise ValueError(f"{len(maps)} depth maps for {len(cams)} cameras")
+    n = dims[0] * dims[1] * dims[2]
+    _abi("mdf_tsdf_integrate", (None if D is None else D.data_ptr(), None if W is None else W.data_ptr(), cdims, corigin, cvoxel,
+                                ctypes.c_float(float(np.float32(trunc))), _src_array(maps), cams.ctypes.data_as(ctypes.c_void_p),
+                                len(maps), h, w, 0 if chunk is None else int(chunk), _stream(maps[0])),
+         tag=f"{dims[0]}x{dims[1]}x{dims[2]} V{len(maps)} {w}x{h}",
+         work={"bytes": (8.0 * 2 * -(-len(maps) // (chunk or TSDF_CHUNK)) + 4.0 * len(maps)) * n, "bound": "hbm"})
+    return D, W
+
+
+def mesh_workspace_bytes(n):
+    return 18 * n + 24 * ((n + MESH_CHUNK - 1) // MESH_CHUNK) + 256      # MDF_MESH_WORKSPACE_BYTES
+
+
+def tsdf_mesh(D, W, origin, voxel, min_weight=1):
+    """Marching tetrahedra over the Kuhn split of the cells of a TSDF volume (D, W [nz,ny,nx] from tsdf_integrate) whose 8 corners
+    have W >= min_weight; a corner is inside where D < 0.  -> (vertices [N,3] fp32, triangles [M,3] int32), vertices in increasing
+    (lattice index, edge direction), triangles in increasing (cell, tetrahedron, triangle), normals towards free space."""
+    _need_gpu(D, W)
+    if D.dim() != 3 or D.shape != W.shape:
+        raise ValueError(f"D {tuple(D.shape)} and W {tuple(W.shape)}: two [nz,ny,nx] volumes are expected")
+    D, W = _f32c(D), _f32c(W)
+    dev = D.device
+    cdims, corigin, cvoxel, dims = _volume_args(origin, voxel, tuple(D.shape)[::-1])
+    n = D.numel()
+    nbytes = mesh_workspace_bytes(n)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    totals = torch.zeros(2, device=dev, dtype=torch.int64)
+    mw = ctypes.c_float(float(min_weight))
+    _abi("mdf_mesh_count", (D.data_ptr(), W.data_ptr(), cdims, corigin, cvoxel, mw, ws.data_ptr(), nbytes, totals.data_ptr(),
+                            _stream(D)), tag=f"{dims[0]}x{dims[1]}x{dims[2]}", work={"bytes": 8.0 * n + 46.0 * n, "bound": "hbm"})
+    nv, nt = (int(x) for x in totals.tolist())
+    vertices = torch.empty((nv if nt else 0, 3), device=dev, dtype=torch.float32)
+    triangles = torch.empty((nt if nv else 0, 3), device=dev, dtype=torch.int32)
+    if nv and nt:
+        _abi("mdf_mesh_emit", (D.data_ptr(), W.data_ptr(), cdims, corigin, cvoxel, mw, ws.data_ptr(), nbytes, nv, nt,
+                               vertices.data_ptr(), triangles.data_ptr(), _stream(D)), tag=f"{dims[0]}x{dims[1]}x{dims[2]}",
+             work={"bytes": 2.0 * n + 12.0 * nv + 12.0 * nt, "bound": "hbm"})
+    return vertices, triangles
+
+
+def mesh_colour(vertices, depths, images, K, E, trunc):
+    """Colour of mesh vertices [N,3] from V views: depths as for tsdf_integrate, images [V,h,w,3] uint8 (or a list).  A view counts
+    for a vertex that lands on its map with a valid depth d and |d - z| <= trunc; the colour is the mean of the nearest texels over
+    those views (in the order given), rounded half up; (128,128,128) where no view counts.  -> uint8 [N,3]."""
+    import numpy as np
+    _need_gpu(vertices)
+    maps = _tsdf_views(depths)
+    imgs = _tsdf_views(images, "images", torch.uint8, (3,))
+    h, w = maps[0].shape
+    if tuple(imgs[0].shape[:2]) != (h, w) or len(imgs) != len(maps):
+        raise ValueError(f"{len(imgs)} images {tuple(imgs[0].shape)} for {len(maps)} depth maps {(h, w)}")
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"vertices {tuple(vertices.shape)}: [N,3] is expected")
+    vtx = _f32c(vertices)
+    n = vtx.shape[0]
+    rgb = torch.empty((n, 3), device=vtx.device, dtype=torch.uint8)
+    cams = tsdf_cameras(K, E)
+    if len(cams) != len(maps):
+        raise ValueError(f"{len(maps)} depth maps for {len(cams)} cameras")
+    if n == 0:
+        return rgb
+    acc = torch.empty((n, 4), device=vtx.device, dtype=torch.float32)
+    _abi("mdf_mesh_colour", (vtx.data_ptr(), n, _src_array(maps), _src_array(imgs), cams.ctypes.data_as(ctypes.c_void_p), len(maps),
+                             h, w, ctypes.c_float(float(np.float32(trunc))), acc.data_ptr(), rgb.data_ptr(), _stream(vtx)),
+         tag=f"N{n} V{len(maps)} {w}x{h}", work={"bytes": (12.0 + 7.0 * len(maps) + 3.0) * n, "bound": "hbm"})
+    return rgb

@@ -142,6 +142,60 @@ def read_ply(path):
     return np.stack([rec["x"], rec["y"], rec["z"]], 1), np.stack([rec["red"], rec["green"], rec["blue"]], 1)
 
 
+_MESH_VERTEX = [("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")]
+_MESH_FACE = [("n", "u1"), ("a", "<i4"), ("b", "<i4"), ("c", "<i4")]
+
+
+def write_ply_mesh(path, xyz, rgb, faces):
+    """A triangle mesh, binary_little_endian 1.0: vertices as write_ply writes them (float x,y,z + uchar red,green,blue, 15 bytes
+    each), then `element face` with `property list uchar int vertex_indices` (a count byte 3 and three int32, 13 bytes each)."""
+    xyz = np.asarray(xyz, dtype="<f4").reshape(-1, 3)
+    rgb = np.asarray(rgb, dtype=np.uint8).reshape(-1, 3)
+    faces = np.asarray(faces).reshape(-1, 3)
+    if len(rgb) != len(xyz):
+        raise ValueError(f"{len(rgb)} colours for {len(xyz)} vertices")
+    if len(faces) and (faces.min() < 0 or faces.max() >= len(xyz)):
+        raise ValueError(f"face indices out of range [0,{len(xyz)})")
+    vert = np.empty(len(xyz), dtype=_MESH_VERTEX)
+    vert["x"], vert["y"], vert["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    vert["red"], vert["green"], vert["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    face = np.empty(len(faces), dtype=_MESH_FACE)
+    face["n"] = 3
+    face["a"], face["b"], face["c"] = faces[:, 0], faces[:, 1], faces[:, 2]
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face %d\n"
+              "property list uchar int vertex_indices\nend_header\n" % (len(vert), len(face)))
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        vert.tofile(f)
+        face.tofile(f)
+
+
+def read_ply_mesh(path):
+    """What write_ply_mesh wrote -> (xyz [N,3] f32, rgb [N,3] u8, faces [M,3] int32)."""
+    with open(path, "rb") as f:
+        nv = nf = None
+        while True:
+            raw = f.readline()
+            if not raw:
+                raise ValueError(f"{path}: PLY header without end_header")
+            line = raw.decode("ascii").strip()
+            if line.startswith("element vertex"):
+                nv = int(line.split()[-1])
+            elif line.startswith("element face"):
+                nf = int(line.split()[-1])
+            elif line == "end_header":
+                break
+        if nv is None or nf is None:
+            raise ValueError(f"{path}: a vertex and a face element are expected")
+        vert = np.fromfile(f, dtype=_MESH_VERTEX, count=nv)
+        face = np.fromfile(f, dtype=_MESH_FACE, count=nf)
+    if len(vert) != nv or len(face) != nf or (nf and not (face["n"] == 3).all()):
+        raise ValueError(f"{path}: truncated, or a face that is not a triangle")
+    return (np.stack([vert["x"], vert["y"], vert["z"]], 1), np.stack([vert["red"], vert["green"], vert["blue"]], 1),
+            np.stack([face["a"], face["b"], face["c"]], 1).astype(np.int32))
+
+
 def tocuda(data_batch, device, parallel=False):
     out = {}
     for k, v in data_batch.items():
