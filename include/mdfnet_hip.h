@@ -273,9 +273,11 @@ int mdf_atv_hypos_fwd(const float* spread, const float* depth, float* hypos_out,
  *   mats [n_src][68] = per view: inverse(K_ref)[9], E_src@inverse(E_ref)[16], K_src[9], inverse(K_src)[9],
  *                       E_ref@inverse(E_src)[16], K_ref[9]  (row-major, computed by the host with the reference's calls)
  *   depth_avg [h,w]; masks [3,h,w] uint8 = (photo, geo, final)
- *   view_masks [n_src,h,w] uint16 (bit i <-> threshold i+2) or NULL; rep_out [n_src,h,w] (depth_reprojected) or NULL   */
+ *   view_masks [n_src,h,w] uint16 (bit i <-> threshold i+2) or NULL; rep_out [n_src,h,w] (depth_reprojected) or NULL
+ *   thre1, thre2 are DOUBLES: the reference compares fp32 tensors with the Python double i / thre, rounded to fp32 once, so the
+ *   eighteen thresholds are (float)(i / thre) of the caller's double (a float thre moves some of them by one ulp).             */
 int mdf_consistency_fuse_fwd(const float* depth_ref, const float* conf, const float* const* src_depths, const float* mats,
-                             int n_src, int h, int w, float photo_threshold, int nconditions, float thre1, float thre2,
+                             int n_src, int h, int w, float photo_threshold, int nconditions, double thre1, double thre2,
                              float* depth_avg, unsigned char* masks, unsigned short* view_masks, float* rep_out, void* stream);
 
 /* ---- DTU depth-map fusion by multi-view consensus (tools/gipuma/main.py -d -> fusibile, fusibile.cu:138-276 with

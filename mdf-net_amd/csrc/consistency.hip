@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256) void consistency_fuse_kernel(const FuseParams 
 
 extern "C" int mdf_consistency_fuse_fwd(const float* depth_ref, const float* conf, const float* const* src_depths,
                                         const float* mats, int n_src, int h, int w, float photo_threshold, int nconditions,
-                                        float thre1, float thre2, float* depth_avg, unsigned char* masks,
+                                        double thre1, double thre2, float* depth_avg, unsigned char* masks,
                                         unsigned short* view_masks, float* rep_out, void* stream) {
   MDF_REQUIRE(depth_ref && conf && src_depths && mats && depth_avg && masks, "null pointer argument");
   MDF_REQUIRE(n_src >= 1 && n_src <= MDF_MAX_SRC_VIEWS, "n_src=%d out of range [1,%d]", n_src, MDF_MAX_SRC_VIEWS);
@@ -178,9 +178,9 @@ extern "C" int mdf_consistency_fuse_fwd(const float* depth_ref, const float* con
     p.src[v] = src_depths[v];
   }
   p.depth_avg = depth_avg; p.masks = masks; p.view_masks = view_masks; p.rep_out = rep_out;
-  for (int i = 0; i < 9; ++i) {            // python: i / thre  (double), compared against float32 tensors
-    p.thr_dist[i] = (float)((double)(i + 2) / (double)thre1);
-    p.thr_rel[i] = (float)((double)(i + 2) / (double)thre2);
+  for (int i = 0; i < 9; ++i) {            // python: i / thre  (double, thre the caller's double), rounded to fp32 ONCE by the compare
+    p.thr_dist[i] = (float)((double)(i + 2) / thre1);
+    p.thr_rel[i] = (float)((double)(i + 2) / thre2);
   }
   p.photo_threshold = photo_threshold;
   p.half_w = (float)((double)(w - 1) / 2.0);

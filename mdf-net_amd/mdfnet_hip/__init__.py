@@ -60,7 +60,7 @@ SIGNATURES = {
     "mdf_range_affine_fwd": (c_int, [c_fp, c_fp, c_fp, c_int, c_fp, c_int, c_i64, c_fp]),
     "mdf_hypos_fit_fwd": (c_int, [c_int, c_fp, c_fp, c_fp, c_int, c_fp, c_fp] + [c_int] * 4 + [c_fp]),
     "mdf_consistency_fuse_fwd": (c_int, [c_fp, c_fp, ctypes.POINTER(c_fp), c_fp, c_int, c_int, c_int, ctypes.c_float, c_int,
-                                         ctypes.c_float, ctypes.c_float, c_fp, c_fp, c_fp, c_fp, c_fp]),
+                                         ctypes.c_double, ctypes.c_double, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "mdf_consensus_fuse_workspace": (c_i64, [c_int, c_int, c_int]),
     "mdf_consensus_fuse_fwd": (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, c_int, c_fp, c_fp, c_fp,
                                        c_i64, c_fp, c_fp, c_fp]),

@@ -832,13 +832,17 @@ def from_nhwc(cl):
 # --------------------------------------------------------------------------- N1: consistency filter / fusion
 def consistency_mats(k_ref, e_ref, src_ks, src_es):
     """HOST: the six matrices per source view the fused kernel consumes, with the reference's own torch calls
-    (dynamic_filter_gpu.py:205,210,226,229) on the CPU.  -> [n_src, 68] float32."""
-    k_ref, e_ref = k_ref.detach().to("cpu", torch.float32), e_ref.detach().to("cpu", torch.float32)
+    (dynamic_filter_gpu.py:205,210,226,229) on the CPU.  -> [n_src, 68] float32.
+    The matrices are made row-major first, as the reference's own are (torch.from_numpy of the camera files): torch.inverse factorises
+    a transposed-storage matrix along another path, whose result differs in the last bit."""
+    def host(m):
+        return m.detach().to("cpu", torch.float32).contiguous()
+    k_ref, e_ref = host(k_ref), host(e_ref)
     rows = []
     with _single_thread():
         kr_inv, er_inv = torch.inverse(k_ref), torch.inverse(e_ref)
         for k, e in zip(src_ks, src_es):
-            k, e = k.detach().to("cpu", torch.float32), e.detach().to("cpu", torch.float32)
+            k, e = host(k), host(e)
             rows.append(torch.cat([kr_inv.reshape(-1), torch.matmul(e, er_inv).reshape(-1), k.reshape(-1),
                                    torch.inverse(k).reshape(-1), torch.matmul(e_ref, torch.inverse(e)).reshape(-1),
                                    k_ref.reshape(-1)]))
@@ -852,15 +856,17 @@ def consistency_fuse(depth_ref, conf, k_ref, e_ref, src_depths, src_ks, src_es, 
     _need_gpu(depth_ref, conf, *src_depths)
     h, w = depth_ref.shape
     dev = depth_ref.device
-    srcs = [_f32c(d) for d in src_depths]
+    # converted copies are held in locals until the launch is enqueued: a temporary's block goes back to the caching allocator as soon
+    # as its data_ptr() is taken, and the next conversion is handed the same block
+    depth_ref, conf, srcs = _f32c(depth_ref), _f32c(conf), [_f32c(d) for d in src_depths]
     mats = consistency_mats(k_ref, e_ref, src_ks, src_es).to(dev, non_blocking=True)
     depth_avg = torch.empty((h, w), device=dev, dtype=torch.float32)
     masks = torch.empty((3, h, w), device=dev, dtype=torch.uint8)
     vm = torch.empty((len(srcs), h, w), device=dev, dtype=torch.int16) if per_view else None
     rep = torch.empty((len(srcs), h, w), device=dev, dtype=torch.float32) if per_view else None
-    _abi("mdf_consistency_fuse_fwd", (_f32c(depth_ref).data_ptr(), _f32c(conf).data_ptr(), _src_array(srcs), mats.data_ptr(),
+    _abi("mdf_consistency_fuse_fwd", (depth_ref.data_ptr(), conf.data_ptr(), _src_array(srcs), mats.data_ptr(),
                                       len(srcs), h, w, ctypes.c_float(photo_threshold), int(nconditions),
-                                      ctypes.c_float(thre1), ctypes.c_float(thre2), depth_avg.data_ptr(), masks.data_ptr(),
+                                      ctypes.c_double(thre1), ctypes.c_double(thre2), depth_avg.data_ptr(), masks.data_ptr(),
                                       None if vm is None else vm.data_ptr(), None if rep is None else rep.data_ptr(),
                                       _stream(depth_avg),),
          tag=f"{w}x{h} nsrc{len(srcs)}", work={"bytes": 4.0 * h * w * (len(srcs) + 3) + 3.0 * h * w, "bound": "hbm"})

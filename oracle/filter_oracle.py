@@ -52,10 +52,12 @@ def _mm(m, rows):
     return out
 
 
-def reproject_explicit(depth_ref, k_ref, e_ref, depth_src, k_src, e_src):
+def reproject_explicit(depth_ref, k_ref, e_ref, depth_src, k_src, e_src, aten_sampler=False):
     """reproject_with_depth with every elementwise step written out (host-independent: the ATen form above depends on the
     host BLAS's accumulation order).  Only the 3x3/4x4 inverses and products come from torch (same calls as the product's
-    host side).  Bit-identical to the reference's output on the build container (tests/test_filter_oracle_cpu.py)."""
+    host side).  Bit-identical to the reference's output on the build container (tests/test_filter_oracle_cpu.py).
+    aten_sampler=True: the "grid_sample form" -- the written-out products around the reference's own bilinear_sampler
+    (F.grid_sample), which holds the restated taps below against ATen's on any host."""
     h, w = depth_ref.shape
     ys, xs = torch.meshgrid(torch.arange(0, h), torch.arange(0, w), indexing="ij")
     x, y = xs.reshape(-1).float(), ys.reshape(-1).float()
@@ -82,12 +84,17 @@ def reproject_explicit(depth_ref, k_ref, e_ref, depth_src, k_src, e_src):
         m = (xf >= 0) & (xf <= w - 1) & (yf >= 0) & (yf <= h - 1)
         xi = torch.nan_to_num(xf, nan=0.0, posinf=0.0, neginf=0.0).clamp(0, w - 1).long()
         yi = torch.nan_to_num(yf, nan=0.0, posinf=0.0, neginf=0.0).clamp(0, h - 1).long()
-        return src[yi * w + xi] * m
+        # a select, not a product: grid_sample's zero padding gives 0 for an out-of-map tap even where the clamped index lands
+        # on a NaN / inf border pixel
+        return torch.where(m, src[yi * w + xi], torch.zeros((), dtype=src.dtype))
 
-    samp = tap(x0, y0) * (fs * fe)
-    samp = _fma(tap(x0 + 1, y0), fs * fw, samp)
-    samp = _fma(tap(x0, y0 + 1), fn * fe, samp)
-    samp = _fma(tap(x0 + 1, y0 + 1), fn * fw, samp)
+    if aten_sampler:
+        samp = bilinear_sampler(depth_src.view(1, 1, h, w), torch.stack((x_src, y_src), dim=-1).view(1, h, w, 2)).reshape(-1)
+    else:
+        samp = tap(x0, y0) * (fs * fe)
+        samp = _fma(tap(x0 + 1, y0), fs * fw, samp)
+        samp = _fma(tap(x0, y0 + 1), fn * fe, samp)
+        samp = _fma(tap(x0 + 1, y0 + 1), fn * fw, samp)
     b = _mm(ks_inv, [x_src * samp, y_src * samp, one * samp])
     r = _mm(t_sr, b + [one])[:3]
     u = _mm(k_ref, r)
@@ -95,11 +102,19 @@ def reproject_explicit(depth_ref, k_ref, e_ref, depth_src, k_src, e_src):
     return r[2].reshape(shp), (u[0] / u[2]).reshape(shp), (u[1] / u[2]).reshape(shp), x_src.reshape(shp), y_src.reshape(shp)
 
 
+def reproject_grid_sample(*args):
+    return reproject_explicit(*args, aten_sampler=True)
+
+
+REPROJECT = {False: reproject_with_depth, True: reproject_explicit, "grid_sample": reproject_grid_sample}
+
+
 def check_geometric_consistency(depth_ref, k_ref, e_ref, depth_src, k_src, e_src, thre1=4, thre2=1300.0, explicit=False):
-    """dynamic_filter_gpu.py:166-191 -> (9 masks for i = 2..10, last mask, depth_reprojected zeroed outside it)."""
+    """dynamic_filter_gpu.py:166-191 -> (9 masks for i = 2..10, last mask, depth_reprojected zeroed outside it).
+    explicit: False (the ATen form), True (the explicit form) or "grid_sample" (the explicit products around F.grid_sample)."""
     h, w = depth_ref.shape
     ys, xs = torch.meshgrid(torch.arange(0, h), torch.arange(0, w), indexing="ij")
-    fn_ = reproject_explicit if explicit else reproject_with_depth
+    fn_ = REPROJECT[explicit]
     depth_rep, xr, yr, _, _ = fn_(depth_ref, k_ref, e_ref, depth_src, k_src, e_src)
     dist = torch.sqrt((xr - xs.unsqueeze(0)) ** 2 + (yr - ys.unsqueeze(0)) ** 2)
     rel = torch.abs(depth_rep - depth_ref) / depth_ref
